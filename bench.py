@@ -1,6 +1,6 @@
 """bench.py — proposals/sec of the per-proposal 6D-pose hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One STEP = one pass of the hot path over `--proposals-per-step` synthetic proposals per GPU, every stage executed:
@@ -9,7 +9,11 @@ hypotheses of an 82k-triangle mesh rasterised (420^2), cropped, pushed through t
 query -> top-3 -> metric (R,t).  Inputs are resident in HBM before the timed region.  Proposals are sharded across
 ranks (weak scaling, no data-path collective); the only collective is the all-gather of 16-float result rows.
 
-Prints ONE JSON line on rank 0 (metric/value/unit/... + "roofline" for the dominant kernel + "cpu_baseline").
+Prints ONE JSON line on rank 0 (metric/value/unit/... + "roofline" for the dominant kernel, from the timed steps themselves).
+A plain run sets up, warms up, times the steps and prints the line.  --full adds the secondary measurements, each outside the
+timed region: the video-tracking workload, the BASELINE config 2 / 3 legs (in memory and through the CLI loops) and the CPU
+baseline ("video_workload", "configs", "cpu_baseline"; null in a plain run).  --dump-outputs DIR writes what the last timed
+step handed its caller as DIR/<name>.npy (float32 / float64); the inputs are seeded, so two builds can be compared file by file.
 """
 from __future__ import annotations
 
@@ -616,6 +620,23 @@ def cli_legs(args, vit, in_memory_meshes_per_s=None):
     return out
 
 
+def dump_outputs(out_dir: Path, results, rows) -> None:
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy per array.  `results` are rank 0's
+    HotPath.run() results (one per proposal), `rows` the all-gathered pack_results() rows of every rank.  Indices are stored
+    as float64 (exact), scores as float32, poses and rows as float64."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {
+        "topk_scores": np.stack([r.topk_scores for r in results]).astype(np.float32),             # [B, k] retrieval scores
+        "topk_idx": np.stack([r.topk_idx for r in results]).astype(np.float64),                   # [B, k] bank rows
+        "hyp_scores": np.stack([r.hyp_scores for r in results]).astype(np.float32),               # [B, 3]
+        "hyp_idx": np.stack([r.hyp_idx for r in results]).astype(np.float64),                     # [B, 3] best hypotheses
+        "TCO": np.stack([np.stack(r.TCO) for r in results]).astype(np.float64),                   # [B, 3, 4, 4] poses
+        "result_rows": rows.double().cpu().numpy(),                                               # [ranks * B, 16]
+    }
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -627,6 +648,11 @@ def main():
     ap.add_argument("--bank", type=int, default=46037)
     ap.add_argument("--mesh-sub", type=int, default=6, help="icosphere subdivisions (6 -> 81 920 triangles)")
     ap.add_argument("--vit-batch", type=int, default=288)   # largest batch whose fc1 output stays below the 4 GiB tile-offset limit; 192 -> 288: -0.6 % (profiles/r04_ab.md)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements outside the timed region: video workload, config 2 / 3 legs, CLI legs, "
+                         "CPU baseline (each can still be switched off by the options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--video-frames", type=int, default=300,
                     help="frames of the secondary video-tracking measurement (BASELINE config 5; 0 = skip)")
@@ -639,6 +665,8 @@ def main():
                     help="tools/ only: load libfreepose_hip_lab.so (measurement variants, FP_* toggles); never a reported number")
     ap.add_argument("--ln-fused", type=int, default=-1, help="fp_ctx_set_option ln_fused (A/B of the LayerNorm fold)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.lab:
         from freepose_amd import _lib
@@ -673,7 +701,7 @@ def main():
     def step():
         res = hp.run(crops, masks, K, boxes, scales)
         rows = pack_results(res).cuda()
-        return parallel.all_gather_rows(rows) if world > 1 else rows
+        return res, (parallel.all_gather_rows(rows) if world > 1 else rows)
 
     for _ in range(args.warmup):
         step()
@@ -685,7 +713,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        rows = step()
+        res, rows = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -702,9 +730,12 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
     who = parallel.rank_report()                                       # backend, RCCL version, device + PCI bus id of every rank
-    video = video_workload(args, vit, rank, world) if args.video_frames > 0 else None    # outside the timed region
-    legs = config_legs(args, vit, bank) if (world == 1 and not args.no_config_legs) else None   # BASELINE configs 2 and 3 (secondary)
-    if world == 1 and not args.no_cli_legs:                            # the same two configs through the CLI loops, files on disk
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), res, rows)
+    # the secondary measurements (--full only), outside the timed region
+    video = video_workload(args, vit, rank, world) if (args.full and args.video_frames > 0) else None
+    legs = config_legs(args, vit, bank) if (args.full and world == 1 and not args.no_config_legs) else None   # BASELINE configs 2 and 3
+    if args.full and world == 1 and not args.no_cli_legs:              # the same two configs through the CLI loops, files on disk
         legs = dict(legs or {})
         legs.update(cli_legs(args, vit, (legs.get("config2_mesh600_420") or {}).get("meshes_per_s")))
 
@@ -745,7 +776,7 @@ def main():
         }
         out["video_workload"] = video
         out["configs"] = legs
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, (mv, mf, mc), bank_f32)
         else:
             out["cpu_baseline"] = None

@@ -200,6 +200,8 @@ def test_missing_checkpoint_fails_closed_and_self_launch_command(tmp_path, monke
         seen["cmd"], seen["env"] = cmd, env
         return 7
     monkeypatch.setattr(subprocess, "call", fake_call)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)             # the command as built on a box without GPUs (the
+                                                                                # device-count refusal: the test below)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     parallel.self_launch(1, ["bench.py"], ["--gpus", "1"])                     # one rank: no launcher, returns

@@ -27,6 +27,7 @@ def _free_port():
 def _worker(rank, world, port, tmp):
     sys.path.insert(0, str(ROOT))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    torch.cuda.is_available = lambda: False     # CPU ranks whatever the box has: no device check, no device in the rank report
     from freepose_amd import parallel
     from oracle import fp_oracle as fo
     r, w, _ = parallel.init_from_env("gloo")

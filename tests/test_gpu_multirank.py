@@ -23,7 +23,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, FP_DIST_BACKEND="gloo", FP_ALLOW_SHARED_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29561", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--hyp", "24",
-           "--bank", "2000", "--mesh-sub", "3", "--vit-batch", "8"]
+           "--bank", "2000", "--mesh-sub", "3", "--vit-batch", "8", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -92,7 +92,7 @@ def test_bench_eight_ranks_on_one_gpu():
     env = dict(os.environ, FP_DIST_BACKEND="gloo", FP_ALLOW_SHARED_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", "29568", str(ROOT / "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--hyp", "24",
-           "--bank", "2000", "--mesh-sub", "3", "--vit-batch", "8", "--video-frames", "16"]
+           "--bank", "2000", "--mesh-sub", "3", "--vit-batch", "8", "--video-frames", "16", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
