@@ -83,6 +83,9 @@ SIGNATURES = {
                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fp_depth_extents": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_void_p,
                                  c_void_p]),
+    "fp_chamfer": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fp_depth_compare": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_void_p, c_void_p]),
     "fp_comm_unique_id": (c_int, [c_void_p]),
     "fp_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "fp_comm_destroy": (c_int, [c_void_p]),

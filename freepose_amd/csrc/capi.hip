@@ -630,6 +630,41 @@ extern "C" int fp_template_score_normed(fp_ctx* ctx, const void* d_tmpl_normed, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// pose-error evaluation (eval.hip)
+extern "C" int fp_chamfer(fp_ctx* ctx, const double* d_pts, int n_pts, const int32_t* d_table, const double* d_xf, int B, int max_n,
+                          int ws_pts, int projected, double* d_out, void* stream) {
+    FP_REQUIRE(ctx && d_pts && d_table && d_xf && d_out, "chamfer: null argument");
+    FP_REQUIRE(B > 0 && B <= 65535, "chamfer: B=%d pairs (1..65535 per call)", B);
+    FP_REQUIRE(n_pts > 0 && max_n > 0 && max_n <= n_pts, "chamfer: n_pts=%d max_n=%d (0 < max_n <= n_pts)", n_pts, max_n);
+    FP_REQUIRE(ws_pts >= 2 && (size_t)ws_pts <= (size_t)2 * B * (size_t)max_n, "chamfer: ws_pts=%d for %d pairs of clouds up to %d points",
+               ws_pts, B, max_n);
+    FP_REQUIRE(projected == 0 || projected == 1, "chamfer: projected=%d (0 or 1)", projected);
+    float* ws;
+    double* slots;
+    int rc;
+    if ((rc = ctx->get("chamfer.cloud", (size_t)ws_pts * 3 * sizeof(float), (void**)&ws))) return rc;
+    if ((rc = ctx->get("chamfer.slots", (size_t)B * 2 * fp_chamfer_chunks(max_n) * sizeof(double), (void**)&slots))) return rc;
+    return fp_chamfer_launch(d_pts, n_pts, d_table, d_xf, B, max_n, ws_pts, projected, ws, slots, d_out, (hipStream_t)stream);
+}
+
+extern "C" int fp_depth_compare(fp_ctx* ctx, const float* d_depth_est, const float* d_depth_gt, int B, int Hh, int W,
+                                const float* d_depth_test, int n_img, const int32_t* d_img_idx, const double* d_params,
+                                const double* d_taus, int n_tau, int32_t* d_out, void* stream) {
+    FP_REQUIRE(ctx && d_depth_est && d_depth_gt && d_out, "depth_compare: null argument");
+    FP_REQUIRE(B > 0 && B <= 65535, "depth_compare: B=%d pairs (1..65535 per call)", B);
+    FP_REQUIRE(Hh > 0 && W > 0 && (size_t)Hh * W <= ((size_t)1 << 30), "depth_compare: image %d x %d", W, Hh);
+    if (d_depth_test) {
+        FP_REQUIRE(d_img_idx && d_params && d_taus, "depth_compare: the VSD counts need d_img_idx, d_params and d_taus");
+        FP_REQUIRE(n_img > 0 && n_tau > 0 && n_tau <= FP_EVAL_MAX_TAUS, "depth_compare: n_img=%d n_tau=%d (n_tau 1..%d)", n_img, n_tau,
+                   FP_EVAL_MAX_TAUS);
+    } else {
+        FP_REQUIRE(n_tau == 0, "depth_compare: n_tau=%d without a test depth image (the CUS counts take none)", n_tau);
+    }
+    return fp_depth_compare_launch(d_depth_est, d_depth_gt, B, Hh, W, d_depth_test, n_img, d_img_idx, d_params, d_taus, n_tau, d_out,
+                                   (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
 // kernel-level entry points
 extern "C" int fp_op_gemm(fp_ctx* ctx, const void* X, int ldx, const void* W, int ldw, void* Cc, int ldc, const void* bias,
                           const void* gamma, const void* resid, int ldr, int M, int N, int K, int epi, void* stream) {

@@ -66,3 +66,12 @@ int fp_rerank_views_launch(const bf16_t* views, const int* offsets, const int* c
                            int Q, int C, int D, int k, hipStream_t s);
 int fp_template_score_launch(const bf16_t* tmpl, const bf16_t* qn, const float* weights, float* dots, float* scores,
                              int T, int P, int D, int templates_normalised, hipStream_t s);
+// eval.hip: pose-error evaluation (chamfer / chamfer_proj, CUS / VSD pixel counts)
+#define FP_EVAL_XF_LD 40      // doubles per pair in fp_chamfer's d_xf
+#define FP_EVAL_TABLE_LD 8    // ints per pair in fp_chamfer's d_table
+#define FP_EVAL_MAX_TAUS 16   // misalignment tolerances counted in one pass of fp_depth_compare
+int fp_chamfer_chunks(int max_n);   // per-block partial sums per (pair, direction)
+int fp_chamfer_launch(const double* pts, int n_pts, const int* table, const double* xf, int B, int max_n, int ws_pts, int projected,
+                      float* ws, double* slots, double* out, hipStream_t s);
+int fp_depth_compare_launch(const float* d_est, const float* d_gt, int B, int Hh, int W, const float* d_test, int n_img, const int* img_idx,
+                            const double* params, const double* taus, int n_tau, int* out, hipStream_t s);

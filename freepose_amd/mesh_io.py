@@ -1,5 +1,6 @@
 """Triangle-mesh container + Wavefront OBJ/MTL reader (the reference uses trimesh.load(path, force='mesh'),
-scripts/dino_inference_video.py:93-101, scripts/render_templates.py:58-66; trimesh is not a dependency here).
+scripts/dino_inference_video.py:93-101, scripts/render_templates.py:58-66; trimesh is not a dependency here) + PLY reader for the BOP
+ground-truth models (bop_toolkit_lib/inout.py:504-537 load_mesh).
 
 Appearance, in the order the rasteriser uses it:
   * per-corner texture coordinates `uv` [F,3,2] + diffuse `texture` [h,w,3] (+ material factor `kd`) -> per-fragment texture
@@ -28,14 +29,21 @@ class TriMesh:
     uv: Optional[np.ndarray] = None               # [F,3,2] float32, OBJ convention (v up)
     texture: Optional[np.ndarray] = None          # [h,w,3] uint8, rows top to bottom
     kd: Optional[np.ndarray] = None               # [3] float32 diffuse factor applied to the texel
+    vertices_f64: Optional[np.ndarray] = None     # [V,3] the vertices as parsed, before the rounding to float32 (load_obj; chamfer clouds)
+
+    @property
+    def pts(self):                       # the key the BOP toolkit's model dictionaries use (inout.load_mesh: model['pts'])
+        return self.vertices
 
     def apply_scale(self, s: float):     # trimesh-compatible (reference mutates the mesh, online_pose_estimator.py:60,64)
         self.vertices = self.vertices * s
+        if self.vertices_f64 is not None:
+            self.vertices_f64 = self.vertices_f64 * s
         return self
 
     def copy(self):
         c = lambda a: None if a is None else np.array(a, copy=True)   # noqa: E731
-        return TriMesh(c(self.vertices), c(self.faces), c(self.vertex_colors), c(self.uv), c(self.texture), c(self.kd))
+        return TriMesh(c(self.vertices), c(self.faces), c(self.vertex_colors), c(self.uv), c(self.texture), c(self.kd), c(self.vertices_f64))
 
 
 def mesh_appearance(mesh) -> dict:
@@ -89,6 +97,12 @@ def device_mesh(mesh):
     return ops.Mesh(v, f, **app)
 
 
+def mesh_cloud_f64(mesh) -> np.ndarray:
+    """[V,3] float64 vertex cloud for the chamfer errors: the unrounded vertices where the reader kept them (TriMesh.vertices_f64)"""
+    v = mesh.vertices_f64 if isinstance(mesh, TriMesh) and mesh.vertices_f64 is not None else mesh.vertices
+    return np.ascontiguousarray(np.asarray(v, dtype=np.float64)).reshape(-1, 3)
+
+
 def mesh_signature(mesh):
     """cheap content check for device-mesh caches: meshes are mutated in place by the pipeline (apply_scale,
     online_pose_estimator.py:60,64) and ids are recycled, so identity alone is not a key"""
@@ -130,7 +144,13 @@ def _load_image(p: Path):
 
 
 def load_obj(path) -> TriMesh:
-    path = Path(path)
+    mesh, v64 = _load_obj(Path(path))
+    if len(v64) == len(mesh.vertices):
+        mesh.vertices_f64 = v64
+    return mesh
+
+
+def _load_obj(path: Path):
     vs, vcol, vts, faces, face_vt, face_mat = [], [], [], [], [], []
     mtllib, cur_mat = None, None
     for line in path.read_text(errors="ignore").splitlines():
@@ -158,16 +178,17 @@ def load_obj(path) -> TriMesh:
         elif t[0] == "usemtl":
             cur_mat = " ".join(t[1:])
     V = np.asarray(vs, dtype=np.float32).reshape(-1, 3)
+    V64 = np.asarray(vs, dtype=np.float64).reshape(-1, 3)
     F = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
     if len(vcol) == len(vs) and vs:
         c = np.asarray(vcol, dtype=np.float32)
         colors = np.clip(c * (255.0 if c.max() <= 1.0 else 1.0) + 0.5, 0, 255).astype(np.uint8)
-        return TriMesh(V, F, colors)
+        return TriMesh(V, F, colors), V64
     mats = _read_mtl(path.parent / mtllib) if mtllib else {}
     if not mats or not len(F):
-        return TriMesh(V, F, None)
+        return TriMesh(V, F, None), V64
     return _with_materials(V, F, np.asarray(vts, np.float32).reshape(-1, 2), np.asarray(face_vt, np.int64).reshape(-1, 3),
-                           face_mat, mats)
+                           face_mat, mats), V64
 
 
 def _with_materials(V, F, vts, face_vt, face_mat, mats) -> TriMesh:
@@ -241,3 +262,102 @@ def _with_materials(V, F, vts, face_vt, face_mat, mats) -> TriMesh:
         uv[i, :, 0] = u
         uv[i, :, 1] = 1.0 - vy / H
     return TriMesh(V, F, None, uv, atlas, None)
+
+
+# ---- PLY ---------------------------------------------------------------------------------------------------------------
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def load_ply(path) -> TriMesh:
+    """PLY as the BOP datasets ship their models: `ascii` or `binary_little_endian`, a vertex element (x y z, optionally red green
+    blue, anything else is skipped) and a face element of triangles.  Vertices stay float64 (`.pts`, like inout.load_mesh)."""
+    data = Path(path).read_bytes()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data[data.index(b"\n", end) + 1:]
+    fmt, elements = None, []                     # elements: [name, count, [(property name, dtype) | (name, count dtype, item dtype)]]
+    for line in data[:end].decode("ascii", errors="ignore").splitlines()[1:]:
+        t = line.split()
+        if not t or t[0] == "comment":
+            continue
+        if t[0] == "format":
+            fmt = t[1]
+        elif t[0] == "element":
+            elements.append([t[1], int(t[2]), []])
+        elif t[0] == "property" and elements:
+            if t[1] == "list":
+                elements[-1][2].append((t[4], _PLY_TYPES[t[2]], _PLY_TYPES[t[3]]))
+            else:
+                elements[-1][2].append((t[2], _PLY_TYPES[t[1]]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: PLY format '{fmt}' (ascii and binary_little_endian are read)")
+    tokens = body.split() if fmt == "ascii" else None
+    pos = 0
+    verts, colors, faces = None, None, np.zeros((0, 3), np.int32)
+    for name, count, props in elements:
+        has_list = any(len(p) == 3 for p in props)
+        if name == "face":
+            if len(props) < 1 or len(props[0]) != 3:
+                raise ValueError(f"{path}: face element without a leading vertex-index list")
+            if fmt == "ascii":
+                rows = []
+                for _ in range(count):
+                    k = int(tokens[pos])
+                    if k != 3:
+                        raise ValueError(f"{path}: only triangular faces are read (found a face with {k} corners)")
+                    rows.append([int(x) for x in tokens[pos + 1:pos + 4]])
+                    pos += 4
+                    for extra in props[1:]:              # e.g. a texcoord list after the indices
+                        pos += (int(tokens[pos]) + 1) if len(extra) == 3 else 1
+                faces = np.asarray(rows, np.int32).reshape(-1, 3)
+            else:
+                if len(props) == 1:                      # the common case in one step
+                    rec = np.dtype([("k", "<" + props[0][1]), ("v", "<" + props[0][2], (3,))])
+                    a = np.frombuffer(body, dtype=rec, count=count, offset=pos)
+                    if count and (a["k"] != 3).any():
+                        raise ValueError(f"{path}: only triangular faces are read")
+                    faces = a["v"].astype(np.int32)
+                    pos += rec.itemsize * count
+                else:
+                    rows = []
+                    for _ in range(count):
+                        for j, pr in enumerate(props):
+                            if len(pr) == 3:
+                                k = int(np.frombuffer(body, "<" + pr[1], 1, pos)[0])
+                                pos += np.dtype(pr[1]).itemsize
+                                v = np.frombuffer(body, "<" + pr[2], k, pos)
+                                pos += np.dtype(pr[2]).itemsize * k
+                                if j == 0:
+                                    if k != 3:
+                                        raise ValueError(f"{path}: only triangular faces are read")
+                                    rows.append(v.astype(np.int32))
+                            else:
+                                pos += np.dtype(pr[1]).itemsize
+                    faces = np.asarray(rows, np.int32).reshape(-1, 3)
+        elif has_list:
+            raise ValueError(f"{path}: list property in element '{name}'")
+        else:
+            names = [p[0] for p in props]
+            if fmt == "ascii":
+                a = np.asarray(tokens[pos:pos + count * len(props)], dtype=np.float64).reshape(count, len(props))
+                pos += count * len(props)
+                col = {n: a[:, i] for i, n in enumerate(names)}
+            else:
+                rec = np.dtype([(n, "<" + d) for n, d in props])
+                a = np.frombuffer(body, dtype=rec, count=count, offset=pos)
+                pos += rec.itemsize * count
+                col = {n: a[n] for n in names}
+            if name == "vertex":
+                verts = np.stack([np.asarray(col[k], np.float64) for k in ("x", "y", "z")], axis=1)
+                if all(k in col for k in ("red", "green", "blue")):
+                    colors = np.stack([np.asarray(col[k]) for k in ("red", "green", "blue")], axis=1).astype(np.uint8)
+    if verts is None:
+        raise ValueError(f"{path}: no vertex element")
+    return TriMesh(verts, faces, colors)
+
+
+def load_mesh(path) -> TriMesh:
+    """by extension: .ply (BOP models) or .obj (retrieved meshes)"""
+    return load_ply(path) if str(path).lower().endswith(".ply") else load_obj(path)

@@ -446,6 +446,129 @@ def depth_extents(depth: torch.Tensor, fx: float, fy: float, cx: float, cy: floa
     return out
 
 
+# ---- pose-error evaluation (csrc/eval.hip) ----------------------------------------------------------
+EVAL_XF_LD, EVAL_TABLE_LD, EVAL_MAX_TAUS = 40, 8, 16      # csrc/internal.h FP_EVAL_*
+EVAL_MAX_PAIRS = 65535                                     # pairs per launch (grid z / y)
+EVAL_MAX_WS_POINTS = 32 << 20                              # centred points held in the context's workspace per launch (12 bytes each)
+
+
+def _per_pair(x, B, shape, what):
+    a = np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
+    if a.size == int(np.prod(shape)):
+        a = np.broadcast_to(a.reshape(shape), (B,) + tuple(shape))
+    if a.size != B * int(np.prod(shape)):
+        raise ValueError(f"{what}: expected {tuple(shape)} or {(B,) + tuple(shape)}, got {a.shape}")
+    return a.reshape((B,) + tuple(shape))
+
+
+def _chamfer(clouds, pairs, s_e, R_e, t_e, R_g, t_g, K):
+    lib = _lib.load()
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    B = pairs.shape[0]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((B,), dtype=torch.float64, device=dev)
+    if B == 0:
+        return out
+    cl = [_dev(torch.as_tensor(c), torch.float64).reshape(-1, 3) for c in clouds]
+    sizes = np.array([c.shape[0] for c in cl], dtype=np.int64)
+    if (sizes <= 0).any():
+        raise ValueError("chamfer: empty vertex cloud")
+    if pairs.min() < 0 or pairs.max() >= len(cl):
+        raise ValueError("chamfer: pair refers to a cloud that was not given")
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    if starts[-1] >= 1 << 31:
+        raise ValueError("chamfer: more than 2^31 vertices in one call")
+    pts = cl[0] if len(cl) == 1 else torch.cat(cl, dim=0)
+    centroid = {}
+    for g in np.unique(pairs[:, 1]):                       # origin of the centred clouds: any point near the object does
+        centroid[int(g)] = cl[int(g)].mean(dim=0).cpu().numpy()
+    xf = np.zeros((B, EVAL_XF_LD), dtype=np.float64)
+    xf[:, 0] = _per_pair(s_e, B, (), "s_e")
+    xf[:, 1:10] = _per_pair(R_e, B, (3, 3), "R_e").reshape(B, 9)
+    xf[:, 10:13] = _per_pair(t_e, B, (3,), "t_e")
+    xf[:, 13:22] = _per_pair(R_g, B, (3, 3), "R_g").reshape(B, 9)
+    xf[:, 22:25] = _per_pair(t_g, B, (3,), "t_g")
+    xf[:, 25:28] = np.stack([centroid[int(g)] for g in pairs[:, 1]])
+    if K is not None:
+        xf[:, 28:37] = _per_pair(K, B, (3, 3), "K").reshape(B, 9)
+    n_e, n_g = sizes[pairs[:, 0]], sizes[pairs[:, 1]]
+    b0 = 0
+    while b0 < B:                                          # launches bounded by the pair count and by the workspace
+        b1, ws = b0, 0
+        while b1 < B and b1 - b0 < EVAL_MAX_PAIRS and (b1 == b0 or ws + n_e[b1] + n_g[b1] <= EVAL_MAX_WS_POINTS):
+            ws += int(n_e[b1] + n_g[b1])
+            b1 += 1
+        if ws >= 1 << 31:
+            raise ValueError("chamfer: one pair of clouds exceeds the workspace index range")
+        nb = b1 - b0
+        table = np.zeros((nb, EVAL_TABLE_LD), dtype=np.int32)
+        table[:, 0], table[:, 1] = starts[pairs[b0:b1, 0]], n_e[b0:b1]
+        table[:, 2], table[:, 3] = starts[pairs[b0:b1, 1]], n_g[b0:b1]
+        slot = np.concatenate([[0], np.cumsum(n_e[b0:b1] + n_g[b0:b1])])
+        table[:, 4], table[:, 5] = slot[:-1], slot[:-1] + n_e[b0:b1]
+        d_table = torch.from_numpy(table).to(dev)
+        d_xf = torch.from_numpy(xf[b0:b1].copy()).to(dev)
+        max_n = int(max(n_e[b0:b1].max(), n_g[b0:b1].max()))
+        check(lib.fp_chamfer(context(), ptr(pts), int(starts[-1]), ptr(d_table), ptr(d_xf), nb, max_n, int(ws), int(K is not None),
+                             C.c_void_p(out.data_ptr() + 8 * b0), current_stream()), "fp_chamfer")
+        b0 = b1
+    return out
+
+
+def chamfer(clouds, pairs, s_e, R_e, t_e, R_g, t_g) -> torch.Tensor:
+    """bidirectional chamfer distance of posed vertex clouds (bop_toolkit pose_error.chamfer) for B pairs at once -> f64 [B] on device.
+    clouds: list of [N_i,3] float64 vertex arrays (numpy or device tensors); pairs int [B,2] = (cloud of the mesh used at inference,
+    cloud of the ground-truth model); s_e [B] scales the inference cloud first; R_* [B,3,3], t_* [B,3] (or one for all pairs)."""
+    return _chamfer(clouds, pairs, s_e, R_e, t_e, R_g, t_g, None)
+
+
+def chamfer_proj(clouds, pairs, s_e, R_e, t_e, R_g, t_g, K) -> torch.Tensor:
+    """chamfer() of the clouds projected by K [3,3] (or [B,3,3]) into the image, in pixels (pose_error.chamfer_proj)"""
+    return _chamfer(clouds, pairs, s_e, R_e, t_e, R_g, t_g, K)
+
+
+def depth_compare(depth_est: torch.Tensor, depth_gt: torch.Tensor, depth_test: Optional[torch.Tensor] = None, img_idx=None, K=None,
+                  delta=None, taus=None, divisor=1.0) -> torch.Tensor:
+    """pixel counts of B pairs of rendered depth images f32 [B,H,W] -> i32 [B,4] = (inter, union of depth > 0, 0, 0): pose_error.cus.
+    With depth_test f32 [n_img,H,W] (+ img_idx [B], K [3,3] | [B,3,3], delta, taus [n_tau], divisor = diameter or 1 per pair):
+    i32 [B, 4 + n_tau] = (inter, union, visib_inter, visib_union, cost-1 pixels per tau): pose_error.vsd."""
+    lib = _lib.load()
+    de, dg = _dev(depth_est, torch.float32), _dev(depth_gt, torch.float32)
+    if de.dim() != 3 or de.shape != dg.shape:
+        raise ValueError(f"depth_compare: depth stacks {tuple(de.shape)} and {tuple(dg.shape)}")
+    B, H, W = de.shape
+    if depth_test is None:
+        out = torch.zeros((B, 4), dtype=torch.int32, device=de.device)
+        for b0 in range(0, B, EVAL_MAX_PAIRS):
+            nb = min(EVAL_MAX_PAIRS, B - b0)
+            check(lib.fp_depth_compare(context(), ptr(de[b0:]), ptr(dg[b0:]), nb, H, W, None, 0, None, None, None, 0, ptr(out[b0:]),
+                                       current_stream()), "fp_depth_compare")
+        return out
+    dt = _dev(depth_test, torch.float32)
+    if dt.dim() == 2:
+        dt = dt[None]
+    if tuple(dt.shape[1:]) != (H, W):
+        raise ValueError(f"depth_compare: test depth {tuple(dt.shape)} for renders of {H} x {W}")
+    tau = np.asarray(taus, dtype=np.float64).reshape(-1)
+    if not 0 < tau.size <= EVAL_MAX_TAUS:
+        raise ValueError(f"depth_compare: {tau.size} taus (1..{EVAL_MAX_TAUS})")
+    idx = np.zeros(B, np.int32) if img_idx is None else np.asarray(img_idx, dtype=np.int32).reshape(B)
+    if B and (idx.min() < 0 or idx.max() >= dt.shape[0]):
+        raise ValueError("depth_compare: img_idx outside the test depth stack")
+    Kb = _per_pair(K, B, (3, 3), "K")
+    prm = np.zeros((B, 8), dtype=np.float64)
+    prm[:, 0], prm[:, 1], prm[:, 2], prm[:, 3] = Kb[:, 0, 0], Kb[:, 1, 1], Kb[:, 0, 2], Kb[:, 1, 2]
+    prm[:, 4] = _per_pair(delta, B, (), "delta")
+    prm[:, 5] = _per_pair(divisor, B, (), "divisor")
+    d_prm, d_idx, d_tau = torch.from_numpy(prm).to(de.device), torch.from_numpy(idx).to(de.device), torch.from_numpy(tau).to(de.device)
+    out = torch.zeros((B, 4 + tau.size), dtype=torch.int32, device=de.device)
+    for b0 in range(0, B, EVAL_MAX_PAIRS):
+        nb = min(EVAL_MAX_PAIRS, B - b0)
+        check(lib.fp_depth_compare(context(), ptr(de[b0:]), ptr(dg[b0:]), nb, H, W, ptr(dt), int(dt.shape[0]), ptr(d_idx[b0:]),
+                                   ptr(d_prm[b0:]), ptr(d_tau), int(tau.size), ptr(out[b0:]), current_stream()), "fp_depth_compare")
+    return out
+
+
 # ---- kernel-level ops (unit tests / microbenchmarks) ------------------------------------------------
 def gemm(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, epi: int = 0, gamma=None, resid=None,
          out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -198,6 +198,36 @@ int fp_rasterize_extents(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses,
 int fp_depth_extents(fp_ctx* ctx, const float* d_depth, int Hn, int Hh, int W, float fx, float fy, float cx,
                      float cy, double* d_out, void* stream);
 
+/* ---- g: pose-error evaluation (bop_toolkit/scripts/eval_calc_errors.py:311-570 and bop_toolkit_lib/pose_error.py; the reference
+ * renders with OpenGL and builds two kd-trees per estimate x ground-truth pair) ------------------------------------------------- */
+/* chamfer (pose_error.py:188-201) and, with projected = 1, chamfer_proj (:204-218) of B pairs in one call:
+ *   d_out[b] = mean_y(min_x |x - y|) + mean_x(min_y |x - y|)    (chamfer_distance(direction='bi', metric='l2'), :143-185; not squared)
+ * over x = posed (projected) vertices of the mesh used at inference, y = those of the ground-truth model.
+ * d_pts f64 [n_pts,3]: the vertex clouds of every model back to back.  d_table i32 [B,8] per pair: {first row of the estimate's cloud in
+ * d_pts, its size, first row of the GT cloud, its size, first slot of the two centred clouds in the workspace (each pair owns size_e +
+ * size_g consecutive slots out of ws_pts), 0, 0}; max_n = the largest cloud size.  d_xf f64 [B,40] per pair: {s_e, R_e[9], t_e[3],
+ * R_g[9], t_g[3], centroid of the GT cloud in its model frame [3], K[9] (projected only), 0...}: pts_e * s_e (eval_calc_errors.py:380),
+ * then misc.transform_pts_Rt / misc.project_pts in fp64; both clouds are centred on the posed (projected) GT centroid before the one
+ * rounding to fp32; exact brute-force minimum of the squared fp32 differences, one fp64 sqrt per point, fixed-order fp64 sums (two
+ * calls give the same bits).  |d_out - reference| <= 2e-6 (r + reference), r = the largest centred coordinate.
+ * The table is device data and cannot be checked by the call: a row whose clouds are empty or reach outside d_pts / the ws_pts slots
+ * is not read or written through, and its d_out is NaN (the call still returns FP_OK). */
+int fp_chamfer(fp_ctx* ctx, const double* d_pts, int n_pts, const int32_t* d_table, const double* d_xf, int B, int max_n, int ws_pts,
+               int projected, double* d_out, void* stream);
+/* pixel counts behind cus (pose_error.py:357-386) and vsd (:17-112) for B pairs of rendered depth images d_depth_est / d_depth_gt
+ * f32 [B,Hh,W] (fp_rasterize_extents output).  Without d_depth_test: d_out i32 [B,4] = {inter, union of depth > 0, 0, 0} and n_tau = 0.
+ * With d_depth_test f32 [n_img,Hh,W] (test depth in the unit of the renders) and d_img_idx i32 [B] (the image of each pair):
+ * d_out i32 [B,4+n_tau] = {inter, union, visib_inter, visib_union, per tau the number of visib_inter pixels with
+ * |dist_gt - dist_est| / divisor >= tau} — misc.depth_im_to_dist_im_fast (misc.py:136-167) in fp64, visibility._estimate_visib_mask
+ * mode bop19 and estimate_visib_mask_est (visibility.py:34-38,74-75) with the float32 difference, step cost (pose_error.py:80-102).
+ * d_params f64 [B,8] = {fx, fy, cx, cy, delta, divisor (the diameter with normalized_by_diameter, else 1), 0, 0}; d_taus f64 [n_tau],
+ * n_tau <= 16, all counted in the same pass.  Every count equals the reference's; the error value is formed by the host.
+ * The depth stacks may have any float alignment: 16-byte loads are used when Hh * W is a multiple of 4 and the three base pointers
+ * are 16-byte aligned, a scalar loop otherwise (same counts).  A d_img_idx outside [0, n_img) gives a row of zeros. */
+int fp_depth_compare(fp_ctx* ctx, const float* d_depth_est, const float* d_depth_gt, int B, int Hh, int W, const float* d_depth_test,
+                     int n_img, const int32_t* d_img_idx, const double* d_params, const double* d_taus, int n_tau, int32_t* d_out,
+                     void* stream);
+
 /* ---- e: multi-GPU.  One process per GPU; RCCL over xGMI.  The reference has no counterpart (SLURM array jobs +
  * files: scripts/dino_inference.py:51-54, merge_results.py); Python hosts use torch.distributed (freepose_amd/parallel.py), these
  * entry points serve hosts without it.  librccl is opened lazily on first use. ------------------------------------------- */
