@@ -19,6 +19,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests._eval_ref import centred_r as _centred_r
+
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 CHAMFER_REL = 2e-6
@@ -52,21 +54,6 @@ def _clouds(gold):
     inf = {"A": gold["mesh_A_v"].astype(np.float64), "T": gold["mesh_T_v"].astype(np.float64)}
     gt = {1: gold["gt_1_v"].astype(np.float64), 2: gold["gt_2_v"].astype(np.float64)}
     return inf, gt
-
-
-def _project(K, R, t, p):
-    q = (K @ (R @ p.T + np.asarray(t).reshape(3, 1))).T
-    return q[:, :2] / q[:, 2:3]
-
-
-def _centred_r(pe, pg, s, Re, te, Rg, tg, K=None):
-    """largest absolute coordinate of the two posed (projected) clouds about the posed (projected) GT centroid"""
-    c = pg.mean(0, keepdims=True)
-    if K is None:
-        X, Y, o = (Re @ (pe * s).T).T + te, (Rg @ pg.T).T + tg, (Rg @ c.T).T + tg
-    else:
-        X, Y, o = _project(K, Re, te, pe * s), _project(K, Rg, tg, pg), _project(K, Rg, tg, c)
-    return float(max(np.abs(X - o).max(), np.abs(Y - o).max()))
 
 
 def _check_chamfer(got, gold, key, K=None):
@@ -156,8 +143,8 @@ def test_depth_compare_scalar_path_and_bad_chamfer_table():
     table[0] = [0, 10, 10, 20, 0, 10, 0, 0]
     table[1] = [0, 10, 25, 20, 30, 40, 0, 0]                 # GT cloud rows 25..44 of 30: outside d_pts
     out = torch.zeros(2, dtype=torch.float64, device="cuda")
-    check(lib.fp_chamfer(ops.context(), ptr(pts), 30, ptr(torch.from_numpy(table).cuda()), ptr(torch.from_numpy(xf).cuda()), 2, 20, 60, 0,
-                         ptr(out), current_stream()), "fp_chamfer")
+    d_table, d_xf = torch.from_numpy(table).cuda(), torch.from_numpy(xf).cuda()   # named: a temporary's block is free for the next upload
+    check(lib.fp_chamfer(ops.context(), ptr(pts), 30, ptr(d_table), ptr(d_xf), 2, 20, 60, 0, ptr(out), current_stream()), "fp_chamfer")
     o = out.cpu().numpy()
     ref = float(torch.cdist(pts[:10], pts[10:]).min(1).values.mean() + torch.cdist(pts[:10], pts[10:]).min(0).values.mean())
     assert np.isnan(o[1]) and abs(o[0] - ref) <= 2e-6 * (float(pts.abs().max()) * 2 + ref)
