@@ -277,6 +277,10 @@ __global__ __launch_bounds__(1024) void compact_flags_kernel(const int32_t* __re
 // X = ((x - cx) / fx) * z: the quotient depends only on the column (row for Y), so it is tabulated once per block in
 // LDS and the per-pixel work is two fp64 multiplies — bit-identical to dividing per pixel, ~10x less fp64 work.
 constexpr int EXT_THREADS = 1024;
+constexpr int EXT_WAVES = EXT_THREADS / 64;
+// the [W] + [Hh] fp64 tables are dynamic LDS; with the kernel's static LDS (< 1 KB) they stay inside the 64 KB every launch may use
+// without an opt-in: H + W <= 8064 (a 1080 x 1920 frame needs 23.4 KB)
+constexpr size_t EXT_LDS_TABLE_BYTES = 63 * 1024;
 __global__ __launch_bounds__(EXT_THREADS) void depth_extents_kernel(const float* __restrict__ depth, int Hh, int W, double fx,
                                                                     double fy, double cx, double cy, double* __restrict__ out) {
     extern __shared__ double tab[];   // [W] column factors, then [Hh] row factors
@@ -310,23 +314,33 @@ __global__ __launch_bounds__(EXT_THREADS) void depth_extents_kernel(const float*
             pixel(d[i], x, y);
         }
     }
-    __shared__ int si[5][EXT_THREADS];
-    __shared__ double sd[4][EXT_THREADS];
-    const int t = threadIdx.x;
-    si[0][t] = cnt; si[1][t] = xmin; si[2][t] = ymin; si[3][t] = xmax; si[4][t] = ymax;
-    sd[0][t] = Xmin; sd[1][t] = Xmax; sd[2][t] = Ymin; sd[3][t] = Ymax;
-    __syncthreads();
-    for (int s = EXT_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            si[0][t] += si[0][t + s];
-            si[1][t] = min(si[1][t], si[1][t + s]); si[2][t] = min(si[2][t], si[2][t + s]);
-            si[3][t] = max(si[3][t], si[3][t + s]); si[4][t] = max(si[4][t], si[4][t + s]);
-            sd[0][t] = fmin(sd[0][t], sd[0][t + s]); sd[1][t] = fmax(sd[1][t], sd[1][t + s]);
-            sd[2][t] = fmin(sd[2][t], sd[2][t + s]); sd[3][t] = fmax(sd[3][t], sd[3][t + s]);
-        }
-        __syncthreads();
+    // integer sums and min / max do not depend on the order: each wave reduces by shuffles, lane 0 leaves one partial per wave in LDS
+    // (under 1 KB of static LDS, so the dynamic tables alone decide what frame size fits — EXT_LDS_TABLE_BYTES)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt += __shfl_down(cnt, off, 64);
+        xmin = min(xmin, __shfl_down(xmin, off, 64)); ymin = min(ymin, __shfl_down(ymin, off, 64));
+        xmax = max(xmax, __shfl_down(xmax, off, 64)); ymax = max(ymax, __shfl_down(ymax, off, 64));
+        Xmin = fmin(Xmin, __shfl_down(Xmin, off, 64)); Xmax = fmax(Xmax, __shfl_down(Xmax, off, 64));
+        Ymin = fmin(Ymin, __shfl_down(Ymin, off, 64)); Ymax = fmax(Ymax, __shfl_down(Ymax, off, 64));
     }
+    __shared__ int si[5][EXT_WAVES];
+    __shared__ double sd[4][EXT_WAVES];
+    const int t = threadIdx.x;
+    if ((t & 63) == 0) {
+        const int w = t >> 6;
+        si[0][w] = cnt; si[1][w] = xmin; si[2][w] = ymin; si[3][w] = xmax; si[4][w] = ymax;
+        sd[0][w] = Xmin; sd[1][w] = Xmax; sd[2][w] = Ymin; sd[3][w] = Ymax;
+    }
+    __syncthreads();
     if (t == 0) {
+        for (int w = 1; w < EXT_WAVES; ++w) {
+            si[0][0] += si[0][w];
+            si[1][0] = min(si[1][0], si[1][w]); si[2][0] = min(si[2][0], si[2][w]);
+            si[3][0] = max(si[3][0], si[3][w]); si[4][0] = max(si[4][0], si[4][w]);
+            sd[0][0] = fmin(sd[0][0], sd[0][w]); sd[1][0] = fmax(sd[1][0], sd[1][w]);
+            sd[2][0] = fmin(sd[2][0], sd[2][w]); sd[3][0] = fmax(sd[3][0], sd[3][w]);
+        }
         int c = si[0][0], bx0 = si[1][0], by0 = si[2][0], bx1 = si[3][0], by1 = si[4][0];
         if (c < 100) {  // mask[105:315, 105:315] = True  (renderer.py:116-117, template.py:75-77)
             const int lo = 105, hx = min(315, W) - 1, hy = min(315, Hh) - 1;
@@ -452,6 +466,8 @@ extern "C" int fp_depth_extents(fp_ctx* ctx, const float* d_depth, int Hn, int H
                                 float cy, double* d_out, void* stream) {
     FP_REQUIRE(ctx && d_depth && d_out, "depth_extents: null argument");
     if (Hn == 0) return FP_OK;
+    FP_REQUIRE(((size_t)Hh + (size_t)W) * sizeof(double) <= EXT_LDS_TABLE_BYTES,
+               "depth_extents: H + W = %d + %d does not fit the kernel's LDS tables (at most %d)", Hh, W, (int)(EXT_LDS_TABLE_BYTES / sizeof(double)));
     hipLaunchKernelGGL(depth_extents_kernel, dim3(Hn), dim3(EXT_THREADS), (size_t)(Hh + W) * sizeof(double), (hipStream_t)stream, d_depth, Hh, W, (double)fx,
                        (double)fy, (double)cx, (double)cy, d_out);
     FP_LAUNCH_CHECK();
