@@ -102,6 +102,11 @@ SIGNATURES = {
                                 c_int, c_int, c_float, c_void_p, c_void_p]),
     "fp_op_gemm_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_int, c_float, c_void_p, c_void_p]),
+    "fp_op_gemm_patch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_void_p]),
+    "fp_op_ln_chain": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                               c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p,
+                               c_void_p, c_void_p]),
     "fp_op_gelu": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fp_op_attention": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fp_op_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -738,6 +738,72 @@ extern "C" int fp_op_gemm_stats(fp_ctx* ctx, const void* X, int ldx, const void*
     FP_HIP(hipMemcpy2DAsync(d_stat + 4, 24, rstd, 4, 4, M, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return FP_OK;
 }
+// Patch-embed GEMM (FP_EPI_PATCH) as fp_vit_forward launches it: row m = b * P + p of X lands in row b * npad + tok_off + p of the token
+// buffer C as bf16(bf16(acc + bias) + pos[p]); the other rows of C (cls, registers, pad) are not touched.
+extern "C" int fp_op_gemm_patch(fp_ctx* ctx, const void* X, int ldx, const void* W, int ldw, void* Cc, int ldc, const void* bias,
+                                const void* pos, int M, int N, int K, int P, int npad, int tok_off, void* stream) {
+    FP_REQUIRE(ctx && X && W && Cc && bias && pos, "op_gemm_patch: null argument");
+    FP_REQUIRE(P > 0 && M > 0 && M % P == 0 && tok_off >= 0 && tok_off + P <= npad && ldc >= N,
+               "op_gemm_patch: M=%d P=%d npad=%d tok_off=%d (M %% P == 0, tok_off + P <= npad, ldc >= N)", M, P, npad, tok_off);
+    FpGemmArgs g{};
+    g.X = (const bf16_t*)X; g.ldx = ldx; g.W = (const bf16_t*)W; g.ldw = ldw; g.C = (bf16_t*)Cc; g.ldc = ldc;
+    g.bias = (const bf16_t*)bias; g.M = M; g.N = N; g.K = K; g.pos = (const bf16_t*)pos; g.P = P; g.npad = npad; g.tok_off = tok_off;
+    g.no_split = ctx->opt_row_split == 0;
+    { const int rc = ctx->sk_scratch(g, (hipStream_t)stream); if (rc) return rc; }
+    return fp_gemm_bf16(g, FP_EPI_PATCH, (hipStream_t)stream);
+}
+// Producer -> consumer pair of the folded LayerNorm as fp_vit_forward chains them (proj -> fc1, fc2 -> qk of the next block):
+//   producer  Y[M,D] = resid + gamma * (X1 W1^T + b1) with FP_EPI_LS_RES_STATS, writing the partial row statistics [D/64][M];
+//   consumer  out[M,N2] (ldo) = LN(Y) W2^T + b2 (mode 0) or its GELU (mode 1) through the LN-folded GEMM on the raw rows of Y.
+// route 0: fp_stats_finalize, then the consumer reads finished row records.  route 1: the consumer launch carries the partial sums
+// (ln_part, ln_part_ld = M, ln_part_nb = D / 64, ln_eps, ln_inv_d = 1 / D) and fp_gemm_bf16 decides who finalises them — the small
+// tiers' prologue, each part of a row split, or the finalisation kernel in front of the big tier (fp_vit_forward never hands the
+// sums to a big-tier launch: it finalises up front when !fp_gemm_fuses_ln_part; route 1 on such a shape pins the fallback in
+// launch_epi, which is the same kernel with the same arguments as route 0).  The row records (16 bytes each)
+// and rstd are poisoned with 0xFF bytes first and copied out afterwards: d_mfrag [M,4] u32, d_rstd [M] f32.
+extern "C" int fp_op_ln_chain(fp_ctx* ctx, const void* X1, int K1, const void* W1, const void* b1, const void* gamma, const void* resid,
+                              void* Y, int M, int D, const void* g_ln, const void* b_ln, float eps, const void* W2, int N2,
+                              const void* b2, int mode, int n_scaled, float row_scale, int route, void* out, int ldo, void* d_mfrag,
+                              float* d_rstd, void* stream) {
+    FP_REQUIRE(ctx && X1 && W1 && b1 && gamma && resid && Y && g_ln && b_ln && W2 && b2 && out && d_mfrag && d_rstd, "op_ln_chain: null argument");
+    FP_REQUIRE((mode == 0 || mode == 1) && (route == 0 || route == 1), "op_ln_chain: mode %d (0..1), route %d (0..1)", mode, route);
+    FP_REQUIRE(M > 0 && D > 0 && D % 64 == 0 && ldo >= N2 && n_scaled >= 0 && n_scaled <= N2, "op_ln_chain: M=%d D=%d N2=%d ldo=%d n_scaled=%d", M, D, N2, ldo, n_scaled);
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t* Wf;
+    uint4 *cb, *stat;
+    float* rstd;
+    float2* part;
+    int rc;
+    if ((rc = ctx->get("op.ln_wf", (size_t)N2 * D * 2, (void**)&Wf))) return rc;
+    if ((rc = ctx->get("op.ln_cb", (size_t)N2 * sizeof(uint4), (void**)&cb))) return rc;
+    if ((rc = ctx->get("op.ln_stat", (size_t)M * sizeof(uint4), (void**)&stat))) return rc;
+    if ((rc = ctx->get("op.ln_rstd", (size_t)M * sizeof(float), (void**)&rstd))) return rc;
+    if ((rc = ctx->get("op.ln_part", (size_t)M * (D / 64) * sizeof(float2), (void**)&part))) return rc;
+    FP_HIP(hipMemsetAsync(stat, 0xFF, (size_t)M * sizeof(uint4), s));
+    FP_HIP(hipMemsetAsync(rstd, 0xFF, (size_t)M * sizeof(float), s));
+    if ((rc = fp_ln_fold((const bf16_t*)W2, (const bf16_t*)g_ln, (const bf16_t*)b_ln, (const bf16_t*)b2, Wf, cb, N2, D, n_scaled, row_scale, s))) return rc;
+    {
+        FpGemmArgs g{};
+        g.X = (const bf16_t*)X1; g.ldx = K1; g.W = (const bf16_t*)W1; g.ldw = K1; g.C = (bf16_t*)Y; g.ldc = D;
+        g.bias = (const bf16_t*)b1; g.gamma = (const bf16_t*)gamma; g.resid = (const bf16_t*)resid; g.ldr = D;
+        g.M = M; g.N = D; g.K = K1; g.stat_part = part; g.no_split = ctx->opt_row_split == 0;
+        if ((rc = ctx->sk_scratch(g, s))) return rc;
+        if ((rc = fp_gemm_bf16(g, FP_EPI_LS_RES_STATS, s))) return rc;
+    }
+    if (route == 0 && (rc = fp_stats_finalize(part, stat, rstd, M, D, eps, s))) return rc;
+    {
+        FpGemmArgs g{};
+        g.X = (const bf16_t*)Y; g.ldx = D; g.W = Wf; g.ldw = D; g.C = (bf16_t*)out; g.ldc = ldo;
+        g.bias = (const bf16_t*)b2; g.M = M; g.N = N2; g.K = D; g.ln_mfrag = stat; g.ln_rstd = rstd; g.ln_cfrag = cb;
+        g.no_split = ctx->opt_row_split == 0;
+        if (route == 1) { g.ln_part = part; g.ln_part_ld = M; g.ln_part_nb = D / 64; g.ln_eps = eps; g.ln_inv_d = 1.0f / (float)D; }
+        if ((rc = ctx->sk_scratch(g, s))) return rc;
+        if ((rc = fp_gemm_bf16(g, mode == 0 ? FP_EPI_LN_BIAS : FP_EPI_LN_GELU, s))) return rc;
+    }
+    FP_HIP(hipMemcpyAsync(d_mfrag, stat, (size_t)M * sizeof(uint4), hipMemcpyDeviceToDevice, s));
+    FP_HIP(hipMemcpyAsync(d_rstd, rstd, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return FP_OK;
+}
 // y = bf16(gelu_erf(x)) elementwise with the direct fp32 expression — the DEFINITION the fc1 epilogue's table is filled from; the
 // tests compare the table-GELU GEMM against it on all 65 536 bf16 inputs
 extern "C" int fp_op_gelu(const void* x, void* y, size_t n, void* stream) {

@@ -273,6 +273,24 @@ int fp_op_ln_linear(fp_ctx* ctx, const void* d_X, int M, int K, const void* d_g_
  * -mean as two-piece bf16 splits —, word 4 rstd = 1 / sigma (f32), word 5 unused. */
 int fp_op_gemm_stats(fp_ctx* ctx, const void* d_X, int ldx, const void* d_W, int ldw, void* d_C, int ldc, const void* d_bias,
                      const void* d_gamma, const void* d_resid, int ldr, int M, int N, int K, float eps, float* d_stat, void* stream);
+/* The patch-embed GEMM of fp_vit_forward (the Conv2d patch_embed.proj of hub DINOv2 behind src/pipeline/retrieval/dino.py:18 as a GEMM
+ * on unfolded patches): row m = b*P + p of d_X lands in row b*npad + tok_off + p of the token buffer d_C (ldc elements per row) as
+ * bf16(bf16(x W^T + bias) + pos[p]); d_pos bf16 [P,N].  M % P == 0, tok_off + P <= npad; the other rows of d_C are not written.
+ * Kernel-level entry used by the tests. */
+int fp_op_gemm_patch(fp_ctx* ctx, const void* d_X, int ldx, const void* d_W, int ldw, void* d_C, int ldc, const void* d_bias,
+                     const void* d_pos, int M, int N, int K, int P, int npad, int tok_off, void* stream);
+/* Producer -> consumer pair of the folded LayerNorm as fp_vit_forward chains them: d_Y bf16 [M,D] = resid + gamma * (X1 W1^T + b1)
+ * (X1 [M,K1], W1 [D,K1], resid [M,D]; the epilogue also writes the partial row statistics), then d_out bf16 [M,N2] (ldo elements per
+ * row) = LN(Y) W2^T + b2 (mode 0) or GELU of it (mode 1) by the LN-folded GEMM, n_scaled / row_scale as in fp_op_ln_linear.
+ * route 0: the statistics are finalised by their own kernel first; route 1: the consumer launch is handed the partial sums with the
+ * fields fp_vit_forward sets and the GEMM dispatch decides where they are finalised (fp_vit_forward itself finalises up front when the
+ * launch takes the big tier and never hands such a launch the sums; route 1 there pins the dispatch's own fallback, which runs the same
+ * finalisation kernel as route 0).  d_mfrag u32 [M,4] and d_rstd f32 [M] receive
+ * the row records (layout: fp_op_gemm_stats) and 1 / sigma the consumer used.  Kernel-level entry used by the tests. */
+int fp_op_ln_chain(fp_ctx* ctx, const void* d_X1, int K1, const void* d_W1, const void* d_b1, const void* d_gamma, const void* d_resid,
+                   void* d_Y, int M, int D, const void* d_g_ln, const void* d_b_ln, float eps, const void* d_W2, int N2,
+                   const void* d_b2, int mode, int n_scaled, float row_scale, int route, void* d_out, int ldo, void* d_mfrag,
+                   float* d_rstd, void* stream);
 /* d_y[i] = bf16(0.5 x (1 + erf(x / sqrt 2))) elementwise on bf16 values in fp32: the direct expression the fc1 epilogue's GELU table
  * is filled from (hub DINOv2 Mlp act_layer = nn.GELU behind src/pipeline/retrieval/dino.py:18-19); the table-GELU GEMM is tested
  * against it on all 65 536 bf16 inputs */
