@@ -86,6 +86,9 @@ SIGNATURES = {
     "fp_chamfer": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fp_depth_compare": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                  c_void_p, c_void_p]),
+    "fp_label_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fp_depthmap_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double,
+                                  c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fp_comm_unique_id": (c_int, [c_void_p]),
     "fp_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "fp_comm_destroy": (c_int, [c_void_p]),

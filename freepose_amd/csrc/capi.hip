@@ -665,6 +665,46 @@ extern "C" int fp_depth_compare(fp_ctx* ctx, const float* d_depth_est, const flo
 }
 
 // ---------------------------------------------------------------------------------------------
+// connected components and the depth-map object scale (scale.hip)
+extern "C" int fp_label_components(fp_ctx* ctx, const uint8_t* d_masks, int n, int H, int W, int connectivity, int32_t* d_labels,
+                                   void* stream) {
+    FP_REQUIRE(ctx && d_masks && d_labels, "label_components: null argument");
+    FP_REQUIRE(connectivity == 4 || connectivity == 8, "label_components: connectivity %d (4 or 8)", connectivity);
+    FP_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W <= ((size_t)1 << 30), "label_components: image %d x %d", W, H);
+    FP_REQUIRE(n >= 0 && n <= 65535, "label_components: n=%d masks (0..65535 per call)", n);
+    if (n == 0) return FP_OK;
+    int* uf;
+    int rc;
+    if ((rc = ctx->get("scale.uf", (size_t)n * H * W * sizeof(int), (void**)&uf))) return rc;
+    return fp_label_launch(d_masks, n, H, W, connectivity, uf, d_labels, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int fp_depthmap_scale(fp_ctx* ctx, const double* d_depth, const uint8_t* d_masks, int n, int H, int W, double fx, double fy,
+                                 double cx, double cy, double erosion_radius, double std_factor, int min_vertices, int align,
+                                 double* d_scale, int32_t* d_info, uint8_t* d_keep, void* stream) {
+    FP_REQUIRE(ctx && d_depth && d_masks && d_scale && d_info, "depthmap_scale: null argument");
+    FP_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W <= ((size_t)1 << 30), "depthmap_scale: image %d x %d", W, H);
+    FP_REQUIRE(n >= 0 && n <= 65535, "depthmap_scale: n=%d masks (0..65535 per call)", n);
+    FP_REQUIRE(erosion_radius > 0.0 && erosion_radius <= 8.0, "depthmap_scale: erosion_radius %g (0 < r <= 8: the distance window)", erosion_radius);
+    FP_REQUIRE(std_factor >= 0.0 && min_vertices >= 1, "depthmap_scale: std_factor %g, min_vertices %d (>= 0, >= 1)", std_factor, min_vertices);
+    FP_REQUIRE(fx != 0.0 && fy != 0.0, "depthmap_scale: focal lengths %g, %g", fx, fy);
+    FP_REQUIRE(align == 0 || align == 1, "depthmap_scale: align=%d (0 or 1)", align);
+    if (n == 0) return FP_OK;
+    const size_t px = (size_t)n * H * W;
+    FpScaleWs ws{};
+    int rc;
+    if ((rc = ctx->get("scale.uf", px * sizeof(int), (void**)&ws.uf))) return rc;
+    if ((rc = ctx->get("scale.labels", px * sizeof(int), (void**)&ws.labels))) return rc;
+    if ((rc = ctx->get("scale.area", px * sizeof(int), (void**)&ws.area))) return rc;
+    if ((rc = ctx->get("scale.d2", px, (void**)&ws.d2))) return rc;
+    if ((rc = ctx->get("scale.kflag", px, (void**)&ws.kflag))) return rc;
+    if ((rc = ctx->get("scale.best", (size_t)n * sizeof(unsigned long long), (void**)&ws.best))) return rc;
+    if ((rc = ctx->get("scale.cnt", (size_t)n * 8 * sizeof(int), (void**)&ws.cnt))) return rc;
+    return fp_depthmap_scale_launch(d_depth, d_masks, n, H, W, fx, fy, cx, cy, erosion_radius, std_factor, min_vertices, align, ws, d_scale,
+                                    d_info, d_keep, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
 // kernel-level entry points
 extern "C" int fp_op_gemm(fp_ctx* ctx, const void* X, int ldx, const void* W, int ldw, void* Cc, int ldc, const void* bias,
                           const void* gamma, const void* resid, int ldr, int M, int N, int K, int epi, void* stream) {

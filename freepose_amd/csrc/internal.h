@@ -75,3 +75,18 @@ int fp_chamfer_launch(const double* pts, int n_pts, const int* table, const doub
                       float* ws, double* slots, double* out, hipStream_t s);
 int fp_depth_compare_launch(const float* d_est, const float* d_gt, int B, int Hh, int W, const float* d_test, int n_img, const int* img_idx,
                             const double* params, const double* taus, int n_tau, int* out, hipStream_t s);
+// scale.hip: connected components and the depth-map object scale (scale_core.h holds the host-checkable index arithmetic)
+struct FpScaleWs {                 // scratch of fp_depthmap_scale_launch, all from the context's workspace
+    int* uf;                       // [n,H,W] union-find labels, later the survivor lists
+    int* labels;                   // [n,H,W] 1 + root, 0 = background
+    int* area;                     // [n,H,W] pixel count on every root
+    uint8_t* d2;                   // [n,H,W] capped squared distance inside the chosen component
+    uint8_t* kflag;                // [n,H,W] kept flags of the survivors
+    unsigned long long* best;      // [n] (area << 32 | ~root) of the chosen component
+    int* cnt;                      // [n,8] survivors per radius of the erosion chain
+};
+// area may be null (labels only)
+int fp_label_launch(const uint8_t* masks, int n, int H, int W, int connectivity, int* uf, int* labels, int* area, hipStream_t s);
+int fp_depthmap_scale_launch(const double* depth, const uint8_t* masks, int n, int H, int W, double fx, double fy, double cx, double cy,
+                             double erosion_radius, double std_factor, int min_vertices, int align, const FpScaleWs& ws, double* scale,
+                             int* info, uint8_t* keep, hipStream_t s);

@@ -446,6 +446,48 @@ def depth_extents(depth: torch.Tensor, fx: float, fy: float, cx: float, cy: floa
     return out
 
 
+# ---- depth-map object scale (csrc/scale.hip) --------------------------------------------------------
+def label_components(masks: torch.Tensor, connectivity: int = 4) -> torch.Tensor:
+    """connected components of binary masks [n,H,W] (or [H,W]) -> int32 labels of the same shape: 0 = background, else 1 + raster
+    index of the component's first pixel; ranked, that is scipy.ndimage.label's numbering (src/pipeline/utils.py:71-84)"""
+    lib = _lib.load()
+    m = _dev(masks)
+    single = m.dim() == 2
+    m = _dev((m[None] if single else m) != 0, torch.uint8)
+    if m.dim() != 3:
+        raise ValueError(f"label_components: masks of shape {tuple(masks.shape)} ([n,H,W] or [H,W])")
+    n, H, W = m.shape
+    out = torch.empty((n, H, W), dtype=torch.int32, device=m.device)
+    check(lib.fp_label_components(context(), ptr(m), n, H, W, int(connectivity), ptr(out), current_stream()), "fp_label_components")
+    return out[0] if single else out
+
+
+def depthmap_scales(depth, masks, K, erosion_radius: float = 8, std_factor: float = 1.5, min_vertices: int = 25, align: bool = True,
+                    return_keep: bool = False):
+    """object scale under each of the n proposal masks [n,H,W] of one image from its float64 depth map [H,W] and intrinsics K [3,3]
+    (reference scale_estimators.py:117-187, one call instead of a host loop) -> (scales f64 [n], info i32 [n,4] = component area,
+    index of the erosion radius used (5 = un-eroded for radius 8), survivor count, points kept) and, with return_keep, the u8 mask
+    [n,H,W] of the pixels whose points entered the extent.  Raises ValueError on an empty mask, like the host function."""
+    lib = _lib.load()
+    d = _dev(torch.as_tensor(depth), torch.float64)
+    m = _dev(torch.as_tensor(masks))
+    m = _dev(m != 0, torch.uint8)
+    if d.dim() != 2 or m.dim() != 3 or tuple(m.shape[1:]) != tuple(d.shape):
+        raise ValueError(f"depthmap_scales: depth {tuple(d.shape)} and masks {tuple(m.shape)} ([H,W] and [n,H,W])")
+    Kn = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float64)
+    n, H, W = m.shape
+    scales = torch.empty((n,), dtype=torch.float64, device=d.device)
+    info = torch.zeros((n, 4), dtype=torch.int32, device=d.device)
+    keep = torch.empty((n, H, W), dtype=torch.uint8, device=d.device) if return_keep else None
+    check(lib.fp_depthmap_scale(context(), ptr(d), ptr(m), n, H, W, float(Kn[0, 0]), float(Kn[1, 1]), float(Kn[0, 2]), float(Kn[1, 2]),
+                                float(erosion_radius), float(std_factor), int(min_vertices), int(bool(align)), ptr(scales), ptr(info),
+                                ptr(keep), current_stream()), "fp_depthmap_scale")
+    empty = (info[:, 0] == 0).nonzero().flatten().tolist()
+    if empty:
+        raise ValueError(f"depthmap scale: empty proposal mask (mask {empty[0]} of {n})")
+    return (scales, info, keep) if return_keep else (scales, info)
+
+
 # ---- pose-error evaluation (csrc/eval.hip) ----------------------------------------------------------
 EVAL_XF_LD, EVAL_TABLE_LD, EVAL_MAX_TAUS = 40, 8, 16      # csrc/internal.h FP_EVAL_*
 EVAL_MAX_PAIRS = 65535                                     # pairs per launch (grid z / y)

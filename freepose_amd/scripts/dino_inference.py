@@ -139,7 +139,12 @@ def process_images(model, templates, dataset, props, images, args):
             from freepose_amd.src.pipeline.estimators.scale_estimators import depthmap_scale
             if "depth" not in entry:
                 raise FileNotFoundError(f"--depth_method depthmap: scene {sid} frame {fid} has no depth map")
-            scales = [depthmap_scale(entry["depth"], entry["intrinsic"], rle_to_mask(p["segmentation"])) for p in sp]
+            if getattr(args, "scale_backend", "host") == "gpu":      # one device call for the image's proposals instead of the host loop
+                from freepose_amd.src.pipeline.estimators.scale_estimators import depthmap_scales
+                masks = np.stack([rle_to_mask(p["segmentation"]) for p in sp])
+                scales = [float(x) for x in depthmap_scales(entry["depth"], entry["intrinsic"], masks)]
+            else:
+                scales = [depthmap_scale(entry["depth"], entry["intrinsic"], rle_to_mask(p["segmentation"])) for p in sp]
             for p, sc in zip(sp, scales):
                 p["scale"] = sc
         else:
@@ -167,6 +172,7 @@ def build_parser():
     ap.add_argument("--allow_random_weights", action="store_true")           # not in the reference: run without the checkpoint
     ap.add_argument("--gpus", type=int, default=1)                           # not in the reference: self-launch N ranks, one per GPU
     ap.add_argument("--read_ahead", type=int, default=2)                     # not in the reference: frames decoded ahead on a thread (0 = the sequential loop)
+    ap.add_argument("--scale_backend", type=str, default="host", choices=["host", "gpu"])   # not in the reference: --depth_method depthmap on the host (numpy / scipy per proposal) or in one device call per image
     ap.add_argument("--image_window", type=int, default=8)                   # not in the reference: images whose proposals share one ViT call and one estimator step (1 = per image, same CSV)
     return ap
 

@@ -71,3 +71,47 @@ def extent_scale(points: np.ndarray) -> float:
 def depthmap_scale(depth, K, mask) -> float:
     """what dino_inference.py:83-84 computes per proposal"""
     return extent_scale(pointcloud_from_depth(depth, K, mask, align=True))
+
+
+def depthmap_scales(depth, K, masks, svd: bool = True) -> np.ndarray:
+    """depthmap_scale for all proposal masks [n,H,W] of one image in ONE device call (freepose_amd.ops.depthmap_scales: connected
+    components, erosion chain, robust cut and extent as HIP kernels) -> float64 [n].  Same discrete decisions as the host function;
+    where ties in |z - median| straddle the cut the device takes them in raster order, the host in whatever order numpy's unstable
+    argsort leaves them (DESIGN "Depth-map scale")."""
+    import torch
+    from freepose_amd import ops
+    m = masks if isinstance(masks, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(masks)).astype(np.uint8))
+    if m.dim() == 2:
+        m = m[None]
+    if m.shape[0] == 0:
+        return np.zeros((0,), dtype=np.float64)
+    d = depth if isinstance(depth, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(depth, dtype=np.float64)))
+    scales, _ = ops.depthmap_scales(d, m, K, align=svd)
+    return scales.cpu().numpy()
+
+
+class ConstantScaleEstimator:
+    """reference scale_estimators.py:12-17"""
+
+    def __init__(self, const) -> None:
+        self.const = const
+
+    def estimate(self, proposals, depth_image=None, K=None):
+        return self.const
+
+
+class MeanScaleEstimator:
+    """reference scale_estimators.py:20-32: depth-map scales of all proposals, rescaled so that their mean diameter is `mean_scale`.
+    The per-mask scales come from one device call."""
+
+    def __init__(self, mean_scale, svd=True):
+        self.mean_scale = mean_scale
+        self.svd = svd
+
+    def estimate(self, proposals, depth_image, K):
+        import torch
+        masks = torch.stack([torch.as_tensor(mask) for mask in proposals.masks])
+        scales = depthmap_scales(depth_image, K, masks, svd=self.svd)
+        correction = self.mean_scale / (2 * np.mean(scales))
+        scales *= correction
+        return scales

@@ -228,6 +228,26 @@ int fp_depth_compare(fp_ctx* ctx, const float* d_depth_est, const float* d_depth
                      int n_img, const int32_t* d_img_idx, const double* d_params, const double* d_taus, int n_tau, int32_t* d_out,
                      void* stream);
 
+/* ---- h: object scale from the scene's depth map (`--depth_method depthmap`, MeanScaleEstimator) ------------------------------------ */
+/* connected components of n binary masks d_masks u8 [n,H,W] (non-zero = foreground), connectivity 4 or 8: what
+ * scipy.ndimage.label(mask, structure) numbers in src/pipeline/utils.py:71-84 (extract_largest_component).  d_labels i32 [n,H,W]:
+ * 0 = background, else 1 + raster index (y * W + x) of the component's first pixel in scan order — ranked, these are scipy's labels.
+ * Union-find with atomicMin on labels that only decrease: exact, and the same output on every call. */
+int fp_label_components(fp_ctx* ctx, const uint8_t* d_masks, int n, int H, int W, int connectivity, int32_t* d_labels, void* stream);
+/* generate_pointcloud + get_scale of src/pipeline/estimators/scale_estimators.py:117-187 for the n proposal masks of one image in one
+ * call: largest 4-connected component (first in scan order among equal areas), isotropic erosion by erosion_radius halved until more
+ * than min_vertices pixels survive (the un-eroded component once a radius below 1 has failed; 0 < erosion_radius <= 8), depth samples
+ * within std_factor population standard deviations of the exact median — never fewer than min_vertices, and only min_vertices when no
+ * sample is farther (the reference's argmax quirk, kept); ties are cut by (|z - median| ascending, raster index ascending) —
+ * back-projection with fx, fy, cx, cy in float64, with align = 1 rotation into the principal axes (`svd=True`), d_scale f64 [n] = half
+ * the largest extent.  d_depth f64 [H,W] is shared by all masks.  d_info i32 [n,4] = {area of the component, index of the radius used
+ * (0 = erosion_radius, 1 = half of it, ...; the number of radii tried = un-eroded: 5 for radius 8), survivor count, points kept}.
+ * d_keep u8 [n,H,W] or NULL: 1 on the pixels whose points entered the extent.  An empty mask gives area 0 and a NaN scale (FP_OK).
+ * Everything but the last floating-point sums is exact; two calls give the same bits. */
+int fp_depthmap_scale(fp_ctx* ctx, const double* d_depth, const uint8_t* d_masks, int n, int H, int W, double fx, double fy, double cx,
+                      double cy, double erosion_radius, double std_factor, int min_vertices, int align, double* d_scale, int32_t* d_info,
+                      uint8_t* d_keep, void* stream);
+
 /* ---- e: multi-GPU.  One process per GPU; RCCL over xGMI.  The reference has no counterpart (SLURM array jobs +
  * files: scripts/dino_inference.py:51-54, merge_results.py); Python hosts use torch.distributed (freepose_amd/parallel.py), these
  * entry points serve hosts without it.  librccl is opened lazily on first use. ------------------------------------------- */
