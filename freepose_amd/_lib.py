@@ -40,6 +40,11 @@ class VitArch(C.Structure):
                 ("n_reg", c_int), ("pos_grid", c_int), ("ln_eps", c_float)]
 
 
+class ClipArch(C.Structure):
+    _fields_ = [("width", c_int), ("depth", c_int), ("heads", c_int), ("mlp_dim", c_int), ("patch", c_int), ("grid", c_int),
+                ("embed_dim", c_int), ("ln_eps", c_float), ("quick_gelu", c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/freepose_hip.h one to one
 SIGNATURES = {
     "fp_last_error": (c_char_p, []),
@@ -114,6 +119,13 @@ SIGNATURES = {
     "fp_op_attention": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fp_op_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "fp_op_im2col_norm": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fp_op_attention_hd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "fp_clip_create": (c_int, [c_void_p, P(ClipArch), P(c_void_p)]),
+    "fp_clip_destroy": (c_int, [c_void_p]),
+    "fp_clip_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p]),
+    "fp_clip_encode_image": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "fp_clip_flops": (c_double, [c_void_p, c_int]),
+    "fp_knn_l2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fp_timer_create": (c_int, [P(c_void_p)]),
     "fp_timer_start": (c_int, [c_void_p, c_void_p]),
     "fp_timer_stop": (c_int, [c_void_p, c_void_p]),

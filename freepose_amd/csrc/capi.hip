@@ -856,6 +856,19 @@ extern "C" int fp_op_attention(const void* QK, int ldqk, const void* Vt, void* O
     return fp_attention_fwd((const bf16_t*)QK, ldqk, (const bf16_t*)Vt, (bf16_t*)O, ldo, B, H, n_tok, npad, q_prescaled != 0,
                             (hipStream_t)stream);
 }
+extern "C" int fp_op_attention_hd(const void* QKV, int ldqkv, void* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad,
+                                  float scale, void* stream) {
+    return fp_attention_hd_fwd((const bf16_t*)QKV, ldqkv, (bf16_t*)O, ldo, B, heads, head_dim, n_tok, npad, scale, (hipStream_t)stream);
+}
+extern "C" int fp_knn_l2(fp_ctx* ctx, const float* d_table, int N, int E, const float* d_queries, int Q, int k, int32_t* d_out_idx,
+                         float* d_out_d2, void* stream) {
+    FP_REQUIRE(ctx, "knn_l2: null context");
+    FP_REQUIRE(N > 0 && Q > 0, "knn_l2: bad shape N=%d Q=%d", N, Q);
+    float* ws = nullptr;      // all Q x N squared distances: O(Q * N) floats of context workspace (a table of a few thousand rows)
+    int rc;
+    if ((rc = ctx->get("knn.d2", (size_t)Q * N * sizeof(float), (void**)&ws))) return rc;
+    return fp_knn_l2_launch(d_table, N, E, d_queries, Q, k, ws, d_out_idx, d_out_d2, (hipStream_t)stream);
+}
 extern "C" int fp_op_im2col_norm(const void* img, void* A, int B, int H, int W, int ps, int KP, void* stream) {
     FP_REQUIRE(img && A && B > 0, "op_im2col_norm: null argument / empty batch");
     return fp_im2col_norm((const bf16_t*)img, (bf16_t*)A, B, H, W, ps, KP, (hipStream_t)stream);

@@ -40,8 +40,12 @@ struct fp_ctx {
 constexpr float FP_ATTN_QSCALE = 1.4426950408889634f / 8.0f;
 int fp_attention_fwd(const bf16_t* QK, int ldqk, const bf16_t* Vt, bf16_t* O, int ldo, int B, int H, int n_tok,
                      int npad, bool q_prescaled, hipStream_t stream);
+// attention_hd.hip: any head dimension (multiple of 8 up to 128) on the plain [q | k | v] output of one bias GEMM
+int fp_attention_hd_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
+                        hipStream_t stream);
 // vit_misc.hip
 int fp_im2col_norm(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps, int KP, hipStream_t s);
+int fp_im2col_norm_ms(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps, int KP, const float* mean, const float* sd, hipStream_t s);
 int fp_token_init(bf16_t* X, const bf16_t* cls, const bf16_t* pos0, const bf16_t* reg, int nreg, int B, int n_tok,
                   int npad, int D, hipStream_t s);
 int fp_layernorm(const bf16_t* X, bf16_t* Y, const bf16_t* gamma, const bf16_t* beta, int rows, int D, float eps,
@@ -66,6 +70,8 @@ int fp_rerank_views_launch(const bf16_t* views, const int* offsets, const int* c
                            int Q, int C, int D, int k, hipStream_t s);
 int fp_template_score_launch(const bf16_t* tmpl, const bf16_t* qn, const float* weights, float* dots, float* scores,
                              int T, int P, int D, int templates_normalised, hipStream_t s);
+int fp_knn_l2_launch(const float* table, int N, int E, const float* queries, int Q, int k, float* d2_ws, int* out_idx, float* out_d2,
+                     hipStream_t s);
 // eval.hip: pose-error evaluation (chamfer / chamfer_proj, CUS / VSD pixel counts)
 #define FP_EVAL_XF_LD 40      // doubles per pair in fp_chamfer's d_xf
 #define FP_EVAL_TABLE_LD 8    // ints per pair in fp_chamfer's d_table

@@ -877,3 +877,73 @@ int fp_rerank_views_launch(const bf16_t* views, const int* offsets, const int* c
     FP_LAUNCH_CHECK();
     return FP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Exact k nearest rows in Euclidean distance: scipy.spatial.KDTree(table).query(queries, k) of GPT4ScaleEstimator
+// (src/pipeline/estimators/scale_estimators.py:48,66) as a brute-force scan.  Squared distances in fp32 in a FIXED order — lane l of a
+// wave adds (t[e] - q[e])^2 for e = l, l + 64, ... with one fmaf each, then the xor butterfly of wave_sum — so equal rows get equal
+// bits and two calls agree.  Results ordered by (distance ascending, row index ascending): attn_hd_core.h fp_knn_key.
+#include "attn_hd_core.h"
+
+namespace {
+
+__global__ __launch_bounds__(256) void knn_dist_kernel(const float* __restrict__ table, const float* __restrict__ queries,
+                                                       float* __restrict__ d2, int N, int E) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const float* t = table + (size_t)row * E;
+    const float* q = queries + (size_t)blockIdx.y * E;
+    float acc = 0.f;
+    for (int e = lane; e < E; e += 64) {
+        const float d = t[e] - q[e];
+        acc = __fmaf_rn(d, d, acc);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) d2[(size_t)blockIdx.y * N + row] = acc;
+}
+
+// one workgroup per query: k rounds, each the minimum key strictly above the previous round's (keys are unique: they carry the row)
+__global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict__ d2, int N, int k, int* __restrict__ out_idx,
+                                                         float* __restrict__ out_d2) {
+    __shared__ unsigned long long red[256];
+    const float* d = d2 + (size_t)blockIdx.x * N;
+    unsigned long long prev = 0ull;
+    for (int j = 0; j < k; ++j) {
+        unsigned long long best = ~0ull;
+        for (int i = threadIdx.x; i < N; i += 256) {
+            const unsigned long long key = fp_knn_key(__float_as_uint(d[i]), (uint32_t)i);
+            if ((j == 0 || key > prev) && key < best) best = key;
+        }
+        red[threadIdx.x] = best;
+        __syncthreads();
+        for (int sft = 128; sft > 0; sft >>= 1) {
+            if ((int)threadIdx.x < sft) {
+                const unsigned long long o = red[threadIdx.x + sft];
+                if (o < red[threadIdx.x]) red[threadIdx.x] = o;
+            }
+            __syncthreads();
+        }
+        prev = red[0];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            out_idx[(size_t)blockIdx.x * k + j] = (int)fp_knn_key_row(prev);
+            out_d2[(size_t)blockIdx.x * k + j] = __uint_as_float(fp_knn_key_bits(prev));
+        }
+    }
+}
+
+}  // namespace
+
+// d2_ws: f32 [Q,N] scratch
+int fp_knn_l2_launch(const float* table, int N, int E, const float* queries, int Q, int k, float* d2_ws, int* out_idx, float* out_d2,
+                     hipStream_t s) {
+    FP_REQUIRE(table && queries && d2_ws && out_idx && out_d2, "knn_l2: null argument");
+    FP_REQUIRE(N > 0 && E > 0 && Q > 0 && Q <= 65535, "knn_l2: bad shape N=%d E=%d Q=%d", N, E, Q);
+    FP_REQUIRE(k >= 1 && k <= 64 && k <= N, "knn_l2: k=%d (1 <= k <= 64 and k <= N=%d)", k, N);
+    hipLaunchKernelGGL(knn_dist_kernel, dim3(cdiv(N, 4), Q), dim3(256), 0, s, table, queries, d2_ws, N, E);
+    FP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(knn_select_kernel, dim3(Q), dim3(256), 0, s, d2_ws, N, k, out_idx, out_d2);
+    FP_LAUNCH_CHECK();
+    return FP_OK;
+}

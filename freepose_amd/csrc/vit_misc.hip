@@ -532,6 +532,18 @@ int fp_im2col_norm(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps, in
     return FP_OK;
 }
 
+// the same kernel with the caller's per-channel mean / std (CLIP's constants: src/pipeline/retrieval/clip.py:12), rounded to bf16 here
+// like torchvision Normalize does on a bf16 tensor
+int fp_im2col_norm_ms(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps, int KP, const float* mean, const float* sd, hipStream_t s) {
+    FP_REQUIRE(H % ps == 0 && W % ps == 0 && KP % 8 == 0 && KP >= 3 * ps * ps, "im2col: bad shape");
+    const long total = (long)B * (H / ps) * (W / ps) * (KP / 8);
+    const int blocks = (int)std::min<long>((total + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(im2col_norm_kernel, dim3(blocks), dim3(256), 0, s, img, A, B, H, W, ps, KP, rbf(mean[0]), rbf(mean[1]), rbf(mean[2]),
+                       rbf(sd[0]), rbf(sd[1]), rbf(sd[2]));
+    FP_LAUNCH_CHECK();
+    return FP_OK;
+}
+
 int fp_token_init(bf16_t* X, const bf16_t* cls, const bf16_t* pos0, const bf16_t* reg, int nreg, int B,
                   int n_tok, int npad, int D, hipStream_t s) {
     const int nrows = 1 + nreg + (npad - n_tok);
@@ -543,13 +555,14 @@ int fp_token_init(bf16_t* X, const bf16_t* cls, const bf16_t* pos0, const bf16_t
 
 int fp_layernorm(const bf16_t* X, bf16_t* Y, const bf16_t* gamma, const bf16_t* beta, int rows, int D, float eps,
                  int rows_per_b, int in_stride_b, int in_off, hipStream_t s, int l2_normalize) {
-    FP_REQUIRE(D % 8 == 0 && D <= 8 * 64 * 3, "layernorm: D=%d unsupported", D);
+    FP_REQUIRE(D % 8 == 0 && D <= 8 * 64 * 4, "layernorm: D=%d unsupported", D);
     if (rows_per_b <= 0) { rows_per_b = rows; in_stride_b = 0; in_off = 0; }
     const int blocks = std::min(cdiv(rows, 4), 256 * 8);
 #define FP_LN(C, L) hipLaunchKernelGGL((layernorm_kernel<C, L>), dim3(blocks), dim3(256), 0, s, X, Y, gamma, beta, rows, D, eps, rows_per_b, in_stride_b, in_off)
     if (D <= 512) { if (l2_normalize) FP_LN(1, 1); else FP_LN(1, 0); }
     else if (D <= 1024) { if (l2_normalize) FP_LN(2, 1); else FP_LN(2, 0); }
-    else { if (l2_normalize) FP_LN(3, 1); else FP_LN(3, 0); }
+    else if (D <= 1536) { if (l2_normalize) FP_LN(3, 1); else FP_LN(3, 0); }
+    else { FP_REQUIRE(!l2_normalize, "layernorm: D=%d with l2_normalize unsupported", D); FP_LN(4, 0); }   // CLIP ViT-bigG/14: 1664
 #undef FP_LN
     FP_LAUNCH_CHECK();
     return FP_OK;

@@ -699,6 +699,147 @@ def attention(qk: torch.Tensor, vt: torch.Tensor, n_tok: int, out: Optional[torc
     return out
 
 
+def attention_hd(qkv: torch.Tensor, heads: int, n_tok: int, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attention for any head dimension (a multiple of 8 up to 128) on the plain output of one bias GEMM (fp_op_attention_hd):
+    qkv bf16 [B, npad, 3*heads*hd], columns [q | k | v] (nn.MultiheadAttention's in_proj order) -> o bf16 [B, npad, heads*hd], the
+    softmax running over the first n_tok tokens of each crop.  scale defaults to 1/sqrt(hd).  `out`: optional bf16 [B, npad, width]
+    whose rows are contiguous B*npad and whose row stride may exceed the width (a column slice of a wider buffer)."""
+    lib = _lib.load()
+    qkv = _dev(qkv, torch.bfloat16)
+    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads) != 0:
+        raise ValueError(f"attention_hd: qkv of shape {tuple(qkv.shape)} ([B, npad, 3*heads*hd]) with heads={heads}")
+    B, npad, w3 = qkv.shape
+    width = w3 // 3
+    hd = width // heads
+    if out is None:
+        out = torch.zeros((B, npad, width), dtype=torch.bfloat16, device=qkv.device)
+    else:
+        assert out.dtype == torch.bfloat16 and out.is_cuda and tuple(out.shape) == (B, npad, width)
+        assert out.stride(2) == 1 and out.stride(0) == npad * out.stride(1)
+    sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(hd))
+    check(lib.fp_op_attention_hd(ptr(qkv), w3, ptr(out), int(out.stride(1)), B, heads, hd, int(n_tok), npad, sc, current_stream()),
+          "fp_op_attention_hd")
+    return out
+
+
+def knn_l2(table: torch.Tensor, queries: torch.Tensor, k: int):
+    """exact k nearest rows of `table` f32 [N,E] for each row of `queries` f32 [Q,E] in Euclidean distance (fp_knn_l2; the brute-force
+    form of scipy.spatial.KDTree(table).query(queries, k)) -> (idx i32 [Q,k], squared distances f32 [Q,k]) ordered by (distance
+    ascending, row index ascending)"""
+    lib = _lib.load()
+    t, q = _dev(torch.as_tensor(table), torch.float32), _dev(torch.as_tensor(queries), torch.float32)
+    if t.dim() != 2 or q.dim() != 2 or t.shape[1] != q.shape[1]:
+        raise ValueError(f"knn_l2: table {tuple(t.shape)} and queries {tuple(q.shape)} ([N,E] and [Q,E])")
+    N, E = t.shape
+    Q = q.shape[0]
+    idx = torch.empty((Q, int(k)), dtype=torch.int32, device=t.device)
+    d2 = torch.empty((Q, int(k)), dtype=torch.float32, device=t.device)
+    if Q > 0:
+        check(lib.fp_knn_l2(context(), ptr(t), N, E, ptr(q), Q, int(k), ptr(idx), ptr(d2), current_stream()), "fp_knn_l2")
+    return idx, d2
+
+
+# ---- CLIP image tower (csrc/clip.hip) -----------------------------------------------------------------
+CLIP_ARCHS = {
+    # name: (width, depth, heads, mlp_dim, embed_dim, patch, grid) — open_clip's model configs (public); all use the exact-erf GELU
+    "ViT-bigG-14": (1664, 48, 16, 8192, 1280, 14, 16),
+    "ViT-H-14": (1280, 32, 16, 5120, 1024, 14, 16),
+    "ViT-L-14": (1024, 24, 16, 4096, 768, 14, 16),
+    # test towers: depth 2, head dimensions 64 / 80 / 104, at 224^2 (257 tokens) and 56^2 (17 tokens); one bigG-wide block
+    "tiny-64": (128, 2, 2, 512, 64, 14, 16), "tiny-80": (320, 2, 4, 640, 64, 14, 16), "tiny-104": (832, 2, 8, 1024, 64, 14, 16),
+    "tiny-64-s56": (128, 2, 2, 512, 64, 14, 4), "tiny-80-s56": (320, 2, 4, 640, 64, 14, 4), "tiny-104-s56": (832, 2, 8, 1024, 64, 14, 4),
+    "tiny-bigG-wide": (1664, 1, 16, 128, 1280, 14, 4),
+}
+
+
+def clip_state_dict_names(model_name: str) -> dict:
+    """open_clip visual state-dict name -> shape"""
+    width, depth, heads, mlp, embed, patch, grid = CLIP_ARCHS[model_name]
+    names = {"conv1.weight": (width, 3, patch, patch), "class_embedding": (width,), "positional_embedding": (1 + grid * grid, width),
+             "ln_pre.weight": (width,), "ln_pre.bias": (width,), "ln_post.weight": (width,), "ln_post.bias": (width,), "proj": (width, embed)}
+    for i in range(depth):
+        p = f"transformer.resblocks.{i}."
+        names.update({p + "ln_1.weight": (width,), p + "ln_1.bias": (width,), p + "attn.in_proj_weight": (3 * width, width),
+                      p + "attn.in_proj_bias": (3 * width,), p + "attn.out_proj.weight": (width, width), p + "attn.out_proj.bias": (width,),
+                      p + "ln_2.weight": (width,), p + "ln_2.bias": (width,), p + "mlp.c_fc.weight": (mlp, width), p + "mlp.c_fc.bias": (mlp,),
+                      p + "mlp.c_proj.weight": (width, mlp), p + "mlp.c_proj.bias": (width,)})
+    return names
+
+
+def random_clip_state_dict(model_name: str, seed: int = 0) -> dict:
+    """seeded random-init weights under open_clip's visual state-dict names (no checkpoint offline): trunc-normal linears,
+    LayerNorm (1 + noise, noise)"""
+    width = CLIP_ARCHS[model_name][0]
+    g = torch.Generator().manual_seed(seed)
+
+    def tn(shape, std=0.02):
+        return torch.nn.init.trunc_normal_(torch.empty(*shape), std=std, a=-2 * std, b=2 * std, generator=g)
+
+    sd = {}
+    for name, shape in clip_state_dict_names(model_name).items():
+        if name.endswith(("ln_pre.weight", "ln_post.weight", "ln_1.weight", "ln_2.weight")):
+            sd[name] = torch.ones(shape) + tn(shape, std=0.05)
+        elif name == "proj":
+            sd[name] = tn(shape, std=width ** -0.5)
+        else:
+            sd[name] = tn(shape)
+    return {k: v.to(torch.bfloat16) for k, v in sd.items()}
+
+
+class ClipVisual:
+    """Device-resident CLIP image tower (open_clip visual state-dict layout) driving fp_clip_encode_image."""
+
+    def __init__(self, model_name: str = "ViT-bigG-14", state_dict: Optional[dict] = None, seed: int = 0, device: Optional[int] = None,
+                 quick_gelu: bool = False):
+        if model_name not in CLIP_ARCHS:
+            raise ValueError(f"unknown CLIP model {model_name}")
+        self.width, self.depth, self.heads, self.mlp_dim, self.embed_dim, self.patch, self.grid = CLIP_ARCHS[model_name]
+        self.model_name = model_name
+        self.image_size = self.patch * self.grid
+        self.lib = _lib.load()
+        self.ctx = context(device)
+        arch = _lib.ClipArch(self.width, self.depth, self.heads, self.mlp_dim, self.patch, self.grid, self.embed_dim, 1e-5, int(bool(quick_gelu)))
+        h = C.c_void_p()
+        check(self.lib.fp_clip_create(self.ctx, C.byref(arch), C.byref(h)), "fp_clip_create")
+        self.handle = h
+        self.weights = {}
+        self.load_state_dict(state_dict if state_dict is not None else random_clip_state_dict(model_name, seed))
+
+    def load_state_dict(self, sd: dict):
+        s = current_stream()
+        want = clip_state_dict_names(self.model_name)
+        missing = sorted(set(want) - set(sd))
+        if missing:
+            raise KeyError(f"CLIP state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
+        for name in want:
+            w = _dev(torch.as_tensor(sd[name]), torch.bfloat16)
+            self.weights[name] = w  # keep alive: the library stores raw pointers
+            check(self.lib.fp_clip_set_weight(self.handle, name.encode(), ptr(w), w.numel(), s), f"set_weight({name})")
+        torch.cuda.synchronize()
+
+    def encode_image(self, images: torch.Tensor) -> torch.Tensor:
+        """bf16 [B,3,S,S] in [0,1] -> bf16 [B, embed_dim]"""
+        x = _dev(images, torch.bfloat16)
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise ValueError(f"CLIP images of shape {tuple(x.shape)} ([B,3,S,S])")
+        B, S = x.shape[0], x.shape[2]
+        out = torch.empty((B, self.embed_dim), dtype=torch.bfloat16, device=x.device)
+        if B > 0:
+            check(self.lib.fp_clip_encode_image(self.handle, ptr(x), B, S, ptr(out), current_stream()), "fp_clip_encode_image")
+        return out
+
+    __call__ = encode_image
+
+    def flops(self, B: int) -> float:
+        return float(self.lib.fp_clip_flops(self.handle, int(B)))
+
+    def __del__(self):
+        try:
+            self.lib.fp_clip_destroy(self.handle)
+        except Exception:
+            pass
+
+
 def im2col_norm(images: torch.Tensor, ps: int = 14, kp: Optional[int] = None) -> torch.Tensor:
     """bf16 crops [B,3,H,W] in [0,1] -> normalised patch rows [B*(H/ps)*(W/ps), kp] (fp_op_im2col_norm; kp defaults to 3*ps*ps rounded
     up to a multiple of 64, what fp_vit_forward uses)"""

@@ -54,4 +54,10 @@ class BOPDataset:
         dp = row.get("depth_path")
         if isinstance(dp, str) and Path(dp).exists():
             out["depth"] = (np.asarray(Image.open(dp)).copy() * 0.1) / 1000
+        # predicted depth (reference base_bop.py:70,74 and bop.py:32-34): <scene>/depth_pred/<frame>.png|jpg, 16-bit / 65535; looked up
+        # next to the image so that index files written before this key existed stay valid
+        rgb = Path(row["rgb_path"])
+        pred = next((p for p in (rgb.parent.parent / "depth_pred" / f"{rgb.stem}{ext}" for ext in (".png", ".jpg")) if p.exists()), None)
+        if pred is not None:
+            out["depth_pred"] = np.asarray(Image.open(pred)).copy() / (2 ** 16 - 1)
         return out

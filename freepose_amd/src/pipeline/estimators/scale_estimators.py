@@ -115,3 +115,75 @@ class MeanScaleEstimator:
         correction = self.mean_scale / (2 * np.mean(scales))
         scales *= correction
         return scales
+
+
+class GPT4ScaleEstimator:
+    """reference scale_estimators.py:35-80: CLIP embedding of each proposal crop -> the `query_k` nearest text embeddings of a table of
+    object names with LLM-given sizes -> median of their sizes -> optionally rescaled so that the median ratio to the depth-map scales
+    of the same image is 1 -> / 2.  The embeddings (one tower call for all crops of the image: a crop's embedding does not depend on
+    its batch), the nearest rows (ops.knn_l2, the brute-force form of the reference's KDTree query; exact ties in index order) and the
+    depth-map scales run on the device; the medians are float64 on the host like the reference's.  The text embeddings are read from
+    `feats_path`: the text tower is not provided, so `scale_file` (which asks for them to be computed) is refused."""
+
+    def __init__(self, clip, query_k=11, scale_file=None, feats_path="data/scale_feats.pt", svd=True) -> None:
+        import torch
+        self.clip = clip
+        self.query_k = query_k
+        self.svd = svd
+        if scale_file is not None:
+            gpt_feats_scales = self.generate_clip_features(scale_file, clip, feats_path=feats_path)
+        else:
+            gpt_feats_scales = torch.load(feats_path, map_location="cpu")
+        self.text_features = torch.as_tensor(gpt_feats_scales["feats"]).float().contiguous()
+        self.scales = torch.as_tensor(gpt_feats_scales["scales"])
+        self._table = self.text_features.cuda()
+
+    def embed(self, proposals):
+        """normalised float32 CLIP embeddings [n, E] of the proposal crops (reference :59-64: bf16 forward, bf16 division by the bf16
+        norm, then float)"""
+        import torch
+        crops = torch.stack([torch.as_tensor(p) for p in proposals.proposals]).to("cuda", dtype=torch.bfloat16)
+        feats = self.clip(crops)
+        with torch.inference_mode():
+            feats = feats / feats.norm(dim=-1, keepdim=True)
+        return feats.float()
+
+    def neighbours(self, image_features):
+        from freepose_amd import ops
+        idx, _ = ops.knn_l2(self._table, image_features, self.query_k)
+        return idx.cpu().numpy().astype(np.int64)
+
+    def estimate(self, proposals, depth_image=None, K=None):
+        import torch
+        assert (depth_image is None) == (K is None)
+        use_depth = depth_image is not None and len(proposals.masks) > 1
+        if use_depth:
+            masks = torch.stack([torch.as_tensor(mask) for mask in proposals.masks])
+            depth_scales = depthmap_scales(depth_image, K, masks, svd=self.svd)
+        idx = self.neighbours(self.embed(proposals))
+        if self.query_k == 1:
+            chatgpt_scales = self.scales[idx[:, 0]].numpy()
+        else:
+            # torch's median of k values: the lower of the middle two for even k
+            chatgpt_scales = self.scales[idx.reshape(-1)].reshape(idx.shape).median(axis=1).values
+        if use_depth:
+            correction = np.median(np.asarray(chatgpt_scales) / depth_scales)
+            scales = depth_scales * correction
+        else:
+            scales = chatgpt_scales
+        return scales / 2.0
+
+    @staticmethod
+    def generate_clip_features(scale_file, clip, feats_path="data/scale_feats.pt"):
+        raise NotImplementedError("the CLIP text tower is not provided: compute the text embeddings of the scale table elsewhere and pass feats_path")
+
+    @staticmethod
+    def mask_to_bbox(mask):
+        import torch
+        if isinstance(mask, torch.Tensor):
+            mask = mask.numpy()
+        rows = np.any(mask, axis=1)
+        cols = np.any(mask, axis=0)
+        rmin, rmax = np.where(rows)[0][[0, -1]]
+        cmin, cmax = np.where(cols)[0][[0, -1]]
+        return rmin, rmax, cmin, cmax

@@ -327,6 +327,48 @@ int fp_op_layernorm(const void* d_X, void* d_Y, const void* d_gamma, const void*
  * columns >= 3*ps*ps zero (the Conv2d patch_embed.proj of hub DINOv2 behind dino.py:18).  Kernel-level entry used by the tests. */
 int fp_op_im2col_norm(const void* d_img, void* d_A, int B, int H, int W, int ps, int KP, void* stream);
 
+/* attention forward for a general head dimension on the plain output of one bias GEMM with N = 3 * width: QKV [B*npad, 3*heads*head_dim]
+ * (ldqkv elements), columns [q | k | v], each heads x head_dim (nn.MultiheadAttention's in_proj order) -> O [B*npad, heads*head_dim]
+ * (ldo elements), O[b,t,h*head_dim+d] = softmax_j(q.k_j * scale) v_j over the n_tok real tokens.  head_dim: a multiple of 8 in [8, 128];
+ * npad % 16 == 0, n_tok <= npad; leading dimensions multiples of 8.  Rows [n_tok, npad) of QKV are never read (they may hold anything);
+ * the same rows of O receive finite values.  bf16 in / out, fp32 accumulation and softmax statistics, any sequence length. */
+int fp_op_attention_hd(const void* d_QKV, int ldqkv, void* d_O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
+                       void* stream);
+
+/* ---- CLIP image tower (src/pipeline/retrieval/clip.py: open_clip encode_image on a bf16 module) --------- */
+typedef struct fp_clip fp_clip;
+typedef struct {
+    int width;      /* 1664 (ViT-bigG/14), 1280 (ViT-H/14), 1024 (ViT-L/14); a multiple of 64          */
+    int depth;      /* 48 / 32 / 24                                                                    */
+    int heads;      /* 16: head dimension width / heads, a multiple of 8 up to 128 (104 / 80 / 64)     */
+    int mlp_dim;    /* 8192 / 5120 / 4096                                                              */
+    int patch;      /* 14                                                                              */
+    int grid;       /* 16: images are (patch * grid)^2, the positional embedding is not interpolated   */
+    int embed_dim;  /* 1280 / 1024 / 768                                                               */
+    float ln_eps;   /* 1e-5                                                                            */
+    int quick_gelu; /* must be 0: only the exact-erf GELU towers are provided                          */
+} fp_clip_arch;
+int fp_clip_create(fp_ctx* ctx, const fp_clip_arch* arch, fp_clip** out);
+int fp_clip_destroy(fp_clip* clip);
+/* Register one tensor (bf16, device) by its open_clip visual state-dict name: conv1.weight, class_embedding, positional_embedding,
+ * ln_pre.{weight,bias}, transformer.resblocks.{i}.{ln_1,ln_2}.{weight,bias}, transformer.resblocks.{i}.attn.{in_proj_weight,in_proj_bias},
+ * transformer.resblocks.{i}.attn.out_proj.{weight,bias}, transformer.resblocks.{i}.mlp.{c_fc,c_proj}.{weight,bias},
+ * ln_post.{weight,bias}, proj ([width, embed_dim], applied as x @ proj).  conv1.weight and proj are copied (padded / transposed); every
+ * other tensor is referenced and must outlive the handle. */
+int fp_clip_set_weight(fp_clip* clip, const char* name, const void* d_tensor, size_t numel, void* stream);
+/* d_images bf16 [B,3,S,S] in [0,1] (S must equal patch * grid) -> d_out bf16 [B, embed_dim]: CLIP mean / std normalisation, patch
+ * conv (no bias), [class; patches] + positional embedding, ln_pre, the blocks, ln_post on the class row, projection. */
+int fp_clip_encode_image(fp_clip* clip, const void* d_images, int B, int S, void* d_out, void* stream);
+double fp_clip_flops(const fp_clip* clip, int B);
+
+/* ---- exact k nearest rows (scipy.spatial.KDTree.query of GPT4ScaleEstimator, scale_estimators.py:48,66) -- */
+/* d_table f32 [N,E], d_queries f32 [Q,E] -> d_out_idx i32 [Q,k], d_out_d2 f32 [Q,k] (SQUARED Euclidean distances, fp32, fixed
+ * summation order), ordered by (distance ascending, row index ascending).  1 <= k <= 64, k <= N.
+ * Brute force, sized for tables of a few thousand rows: the context keeps a workspace of Q * N floats (all squared distances; O(Q * N)
+ * device memory, reused between calls), and the selection makes k serial passes over a query's N distances — O(Q * N * (E + k)) work. */
+int fp_knn_l2(fp_ctx* ctx, const float* d_table, int N, int E, const float* d_queries, int Q, int k, int32_t* d_out_idx, float* d_out_d2,
+              void* stream);
+
 /* ---- measurement helpers (bench.py: HIP-event timing on the launch stream) ----------------------------- */
 int fp_timer_create(void** out);
 int fp_timer_start(void* timer, void* stream);
