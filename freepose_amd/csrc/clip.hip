@@ -10,19 +10,13 @@
 // the LayerNorm kernel, token_init with no register tokens, and attention_hd.hip (ViT-bigG/14 has 16 heads of 104).  The LayerNorm-folded
 // GEMM route of the DINOv2 driver is not used: its statistics kernel stops at 1536 features.
 #include <stdio.h>
-#include <string.h>
 
 #include <cmath>
 
 #include "../../include/freepose_hip.h"
-#include "internal.h"
+#include "tower_steps.h"
 
 namespace {
-
-struct ClipBlockW {
-    const bf16_t *ln1w = nullptr, *ln1b = nullptr, *inw = nullptr, *inb = nullptr, *outw = nullptr, *outb = nullptr, *ln2w = nullptr,
-                 *ln2b = nullptr, *fcw = nullptr, *fcb = nullptr, *pjw = nullptr, *pjb = nullptr;
-};
 
 // dst [cols, rows] = src [rows, cols]^T (the projection is stored [width, embed_dim] and applied as x @ proj; the GEMM wants [out, in])
 __global__ void transpose_bf16_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int rows, int cols) {
@@ -33,20 +27,21 @@ __global__ void transpose_bf16_kernel(const bf16_t* __restrict__ src, bf16_t* __
     }
 }
 
+constexpr float CLIP_MEAN[3] = {0.48145466f, 0.4578275f, 0.40821073f}, CLIP_SD[3] = {0.26862954f, 0.26130258f, 0.27577711f};   // clip.py:12
+
 }  // namespace
 
 struct fp_clip {
     fp_ctx* ctx = nullptr;
     fp_clip_arch a{};
-    int KP = 0;                   // padded patch-embed K
+    TowerEmbedW emb;              // no bias (zeros), no register tokens
     int head_dim = 0;
-    const bf16_t *cls = nullptr, *pos = nullptr, *lnprew = nullptr, *lnpreb = nullptr, *lnpostw = nullptr, *lnpostb = nullptr;
-    bf16_t* pe_w = nullptr;       // [width, KP] private padded copy of conv1.weight
+    const bf16_t *lnprew = nullptr, *lnpreb = nullptr, *lnpostw = nullptr, *lnpostb = nullptr;
     bf16_t* projT = nullptr;      // [embed_dim, width] private transposed copy of proj
     bf16_t* ones = nullptr;       // gamma of the residual epilogue (no LayerScale in CLIP)
     bf16_t* zeros = nullptr;      // bias of the patch and projection GEMMs (neither layer has one)
     bool have_conv = false, have_proj = false;
-    std::vector<ClipBlockW> blk;
+    std::vector<TowerBlockW> blk;
 };
 
 extern "C" int fp_clip_create(fp_ctx* ctx, const fp_clip_arch* arch, fp_clip** out) {
@@ -64,28 +59,30 @@ extern "C" int fp_clip_create(fp_ctx* ctx, const fp_clip_arch* arch, fp_clip** o
     v->a = *arch;
     v->head_dim = hd;
     v->blk.resize(arch->depth);
-    v->KP = cdiv(3 * arch->patch * arch->patch, 64) * 64;
+    v->emb.patch = arch->patch; v->emb.mean = CLIP_MEAN; v->emb.sd = CLIP_SD;
+    v->emb.KP = cdiv(3 * arch->patch * arch->patch, 64) * 64;
     const size_t W = arch->width, E = arch->embed_dim, nvec = std::max(W, E);
-    if (hipMalloc((void**)&v->pe_w, W * v->KP * 2) != hipSuccess || hipMalloc((void**)&v->projT, E * W * 2) != hipSuccess ||
+    if (hipMalloc((void**)&v->emb.pe_w, W * v->emb.KP * 2) != hipSuccess || hipMalloc((void**)&v->projT, E * W * 2) != hipSuccess ||
         hipMalloc((void**)&v->ones, nvec * 2) != hipSuccess || hipMalloc((void**)&v->zeros, nvec * 2) != hipSuccess) {
         fp_set_error("clip_create: hipMalloc failed");
         fp_clip_destroy(v);
         return FP_ERR_HIP;
     }
     std::vector<bf16_t> one(nvec, f2bf(1.0f));
-    if (hipMemset(v->pe_w, 0, W * v->KP * 2) != hipSuccess || hipMemset(v->zeros, 0, nvec * 2) != hipSuccess ||
+    if (hipMemset(v->emb.pe_w, 0, W * v->emb.KP * 2) != hipSuccess || hipMemset(v->zeros, 0, nvec * 2) != hipSuccess ||
         hipMemcpy(v->ones, one.data(), nvec * 2, hipMemcpyHostToDevice) != hipSuccess) {
         fp_set_error("clip_create: initialising the device buffers failed");
         fp_clip_destroy(v);
         return FP_ERR_HIP;
     }
+    v->emb.pe_b = v->zeros;
     *out = v;
     return FP_OK;
 }
 
 extern "C" int fp_clip_destroy(fp_clip* v) {
     if (!v) return FP_OK;
-    if (v->pe_w) (void)hipFree(v->pe_w);
+    if (v->emb.pe_w) (void)hipFree(v->emb.pe_w);
     if (v->projT) (void)hipFree(v->projT);
     if (v->ones) (void)hipFree(v->ones);
     if (v->zeros) (void)hipFree(v->zeros);
@@ -99,45 +96,35 @@ extern "C" int fp_clip_set_weight(fp_clip* v, const char* name, const void* d, s
     const bf16_t* p = (const bf16_t*)d;
     const size_t D = a.width, M = a.mlp_dim, E = a.embed_dim;
     hipStream_t s = (hipStream_t)stream;
-    auto need = [&](size_t n) -> bool {
-        if (numel != n) { fp_set_error("clip_set_weight: %s has %zu elements, expected %zu", name, numel, n); return false; }
-        return true;
-    };
     std::string nm(name);
     if (nm == "conv1.weight") {
-        const size_t K = (size_t)3 * a.patch * a.patch;
-        if (!need(D * K)) return FP_ERR_INVALID;
-        FP_HIP(hipMemcpy2DAsync(v->pe_w, (size_t)v->KP * 2, p, K * 2, K * 2, D, hipMemcpyDeviceToDevice, s));
-        v->have_conv = true;
-        return FP_OK;
+        const int rc = fp_tower_set_patch_weight("clip_set_weight", name, p, numel, v->emb, D, s);
+        v->have_conv |= rc == FP_OK;
+        return rc;
     }
     if (nm == "proj") {
-        if (!need(D * E)) return FP_ERR_INVALID;
+        if (!fp_weight_numel("clip_set_weight", name, numel, D * E)) return FP_ERR_INVALID;
         hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)std::min<size_t>((D * E + 255) / 256, 4096)), dim3(256), 0, s, p, v->projT, (int)D, (int)E);
         FP_LAUNCH_CHECK();
         v->have_proj = true;
         return FP_OK;
     }
-    if (nm == "class_embedding") { if (!need(D)) return FP_ERR_INVALID; v->cls = p; return FP_OK; }
-    if (nm == "positional_embedding") { if (!need((size_t)(1 + a.grid * a.grid) * D)) return FP_ERR_INVALID; v->pos = p; return FP_OK; }
-    if (nm == "ln_pre.weight") { if (!need(D)) return FP_ERR_INVALID; v->lnprew = p; return FP_OK; }
-    if (nm == "ln_pre.bias") { if (!need(D)) return FP_ERR_INVALID; v->lnpreb = p; return FP_OK; }
-    if (nm == "ln_post.weight") { if (!need(D)) return FP_ERR_INVALID; v->lnpostw = p; return FP_OK; }
-    if (nm == "ln_post.bias") { if (!need(D)) return FP_ERR_INVALID; v->lnpostb = p; return FP_OK; }
+    const WeightEnt top[] = {{"class_embedding", &v->emb.cls, D}, {"positional_embedding", &v->emb.pos, (size_t)(1 + a.grid * a.grid) * D},
+                             {"ln_pre.weight", &v->lnprew, D}, {"ln_pre.bias", &v->lnpreb, D}, {"ln_post.weight", &v->lnpostw, D},
+                             {"ln_post.bias", &v->lnpostb, D}};
+    if (const int hit = fp_set_named_weight("clip_set_weight", name, name, top, p, numel)) return hit > 0 ? FP_OK : FP_ERR_INVALID;
     int bi = -1;
     char rest[64] = {0};
     if (sscanf(name, "transformer.resblocks.%d.%63s", &bi, rest) == 2 && bi >= 0 && bi < a.depth) {
-        ClipBlockW& w = v->blk[bi];
-        std::string r(rest);
-        struct Ent { const char* n; const bf16_t** slot; size_t numel; } tab[] = {
-            {"ln_1.weight", &w.ln1w, D}, {"ln_1.bias", &w.ln1b, D},
-            {"attn.in_proj_weight", &w.inw, 3 * D * D}, {"attn.in_proj_bias", &w.inb, 3 * D},
-            {"attn.out_proj.weight", &w.outw, D * D}, {"attn.out_proj.bias", &w.outb, D},
-            {"ln_2.weight", &w.ln2w, D}, {"ln_2.bias", &w.ln2b, D},
-            {"mlp.c_fc.weight", &w.fcw, M * D}, {"mlp.c_fc.bias", &w.fcb, M},
-            {"mlp.c_proj.weight", &w.pjw, D * M}, {"mlp.c_proj.bias", &w.pjb, D}};
-        for (auto& e : tab)
-            if (r == e.n) { if (!need(e.numel)) return FP_ERR_INVALID; *e.slot = p; return FP_OK; }
+        TowerBlockW& w = v->blk[bi];
+        const WeightEnt tab[] = {
+            {"ln_1.weight", &w.n1w, D}, {"ln_1.bias", &w.n1b, D},
+            {"attn.in_proj_weight", &w.qkvw, 3 * D * D}, {"attn.in_proj_bias", &w.qkvb, 3 * D},
+            {"attn.out_proj.weight", &w.projw, D * D}, {"attn.out_proj.bias", &w.projb, D},
+            {"ln_2.weight", &w.n2w, D}, {"ln_2.bias", &w.n2b, D},
+            {"mlp.c_fc.weight", &w.fc1w, M * D}, {"mlp.c_fc.bias", &w.fc1b, M},
+            {"mlp.c_proj.weight", &w.fc2w, D * M}, {"mlp.c_proj.bias", &w.fc2b, D}};
+        if (const int hit = fp_set_named_weight("clip_set_weight", name, rest, tab, p, numel)) return hit > 0 ? FP_OK : FP_ERR_INVALID;
     }
     fp_set_error("clip_set_weight: unknown tensor name '%s'", name);
     return FP_ERR_INVALID;
@@ -150,12 +137,10 @@ extern "C" int fp_clip_encode_image(fp_clip* v, const void* d_images, int B, int
     FP_REQUIRE(B > 0, "clip_encode_image: B=%d", B);
     FP_REQUIRE(S == a.patch * a.grid, "clip_encode_image: images are %d x %d, the tower takes %d x %d (patch %d, grid %d: the positional "
                "embedding is not interpolated)", S, S, a.patch * a.grid, a.patch * a.grid, a.patch, a.grid);
-    FP_REQUIRE(v->have_conv && v->have_proj && v->cls && v->pos && v->lnprew && v->lnpreb && v->lnpostw && v->lnpostb,
+    FP_REQUIRE(v->have_conv && v->have_proj && v->emb.cls && v->emb.pos && v->lnprew && v->lnpreb && v->lnpostw && v->lnpostb,
                "clip_encode_image: embedding / ln_pre / ln_post / proj weights not set");
     for (int i = 0; i < a.depth; ++i) {
-        const ClipBlockW& w = v->blk[i];
-        FP_REQUIRE(w.ln1w && w.ln1b && w.inw && w.inb && w.outw && w.outb && w.ln2w && w.ln2b && w.fcw && w.fcb && w.pjw && w.pjb,
-                   "clip_encode_image: weights of block %d not set", i);
+        FP_REQUIRE(v->blk[i].complete(), "clip_encode_image: weights of block %d not set", i);
     }
     const int D = a.width, P = a.grid * a.grid, n_tok = P + 1;
     const int npad = cdiv(n_tok, 16) * 16;
@@ -165,55 +150,33 @@ extern "C" int fp_clip_encode_image(fp_clip* v, const void* d_images, int B, int
 
     bf16_t *A0, *X, *Y, *QKV, *AO, *H1, *POOL;
     int rc;
-    if ((rc = v->ctx->get("clip.im2col", (size_t)B * P * v->KP * 2, (void**)&A0))) return rc;
-    if ((rc = v->ctx->get("clip.x", M * D * 2, (void**)&X))) return rc;
-    if ((rc = v->ctx->get("clip.y", M * D * 2, (void**)&Y))) return rc;
-    if ((rc = v->ctx->get("clip.qkv", M * 3 * D * 2, (void**)&QKV))) return rc;
-    if ((rc = v->ctx->get("clip.ao", M * D * 2, (void**)&AO))) return rc;
-    if ((rc = v->ctx->get("clip.h1", M * (size_t)a.mlp_dim * 2, (void**)&H1))) return rc;
-    if ((rc = v->ctx->get("clip.pool", (size_t)B * D * 2, (void**)&POOL))) return rc;
-    const int nosplit = v->ctx->opt_row_split == 0;
-    auto gemm = [&](const bf16_t* Xp, int ldx, const bf16_t* Wp, int K, bf16_t* Cp, int N, const bf16_t* bias, int rows, int epi,
-                    const bf16_t* resid) -> int {
-        FpGemmArgs g{};
-        g.no_split = nosplit;
-        int r = v->ctx->sk_scratch(g, s);
-        if (r) return r;
-        g.X = Xp; g.ldx = ldx; g.W = Wp; g.ldw = K; g.C = Cp; g.ldc = N; g.bias = bias; g.M = rows; g.N = N; g.K = K;
-        if (resid) { g.gamma = v->ones; g.resid = resid; g.ldr = N; }
-        return fp_gemm_bf16(g, epi, s);
-    };
+    fp_ctx* ctx = v->ctx;
+    FP_WS(ctx, "clip.im2col", (size_t)B * P * v->emb.KP * 2, A0);
+    FP_WS(ctx, "clip.x", M * D * 2, X);
+    FP_WS(ctx, "clip.y", M * D * 2, Y);
+    FP_WS(ctx, "clip.qkv", M * 3 * D * 2, QKV);
+    FP_WS(ctx, "clip.ao", M * D * 2, AO);
+    FP_WS(ctx, "clip.h1", M * (size_t)a.mlp_dim * 2, H1);
+    FP_WS(ctx, "clip.pool", (size_t)B * D * 2, POOL);
 
-    // ---- normalise + unfold, patch GEMM scattering into the token buffer, class row, ln_pre ----------------------------------------
-    const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, sd[3] = {0.26862954f, 0.26130258f, 0.27577711f};   // clip.py:12
-    if ((rc = fp_im2col_norm_ms((const bf16_t*)d_images, A0, B, S, S, a.patch, v->KP, mean, sd, s))) return rc;
-    if ((rc = fp_token_init(X, v->cls, v->pos, nullptr, 0, B, n_tok, npad, D, s))) return rc;
-    {
-        FpGemmArgs g{};
-        g.no_split = nosplit;
-        if ((rc = v->ctx->sk_scratch(g, s))) return rc;
-        g.X = A0; g.ldx = v->KP; g.W = v->pe_w; g.ldw = v->KP; g.C = X; g.ldc = D; g.bias = v->zeros;
-        g.M = B * P; g.N = D; g.K = v->KP; g.pos = v->pos + D; g.P = P; g.npad = npad; g.tok_off = 1;
-        if ((rc = fp_gemm_bf16(g, FP_EPI_PATCH, s))) return rc;
-    }
-    if ((rc = fp_layernorm(X, Y, v->lnprew, v->lnpreb, Mi, D, a.ln_eps, 0, 0, 0, s))) return rc;
     bf16_t* R = Y;    // residual stream
     bf16_t* T = X;    // LayerNorm output of the current half block
+    const TowerRun t{ctx, nullptr, s, B, n_tok, npad, D, a.mlp_dim, a.ln_eps, R, T, AO, H1, v->ones};
+    // ---- normalise + unfold, patch GEMM scattering into the token buffer, class row, ln_pre ----------------------------------------
+    if ((rc = fp_tower_embed(t, v->emb, v->emb.pos + D, (const bf16_t*)d_images, S, S, A0, X))) return rc;
+    if ((rc = fp_layernorm(X, Y, v->lnprew, v->lnpreb, Mi, D, a.ln_eps, 0, 0, 0, s))) return rc;
     const float scale = 1.0f / sqrtf((float)v->head_dim);
     for (int i = 0; i < a.depth; ++i) {
-        const ClipBlockW& w = v->blk[i];
-        if ((rc = fp_layernorm(R, T, w.ln1w, w.ln1b, Mi, D, a.ln_eps, 0, 0, 0, s))) return rc;
-        if ((rc = gemm(T, D, w.inw, D, QKV, 3 * D, w.inb, Mi, FP_EPI_BIAS, nullptr))) return rc;
+        const TowerBlockW& w = v->blk[i];
+        if ((rc = fp_layernorm(R, T, w.n1w, w.n1b, Mi, D, a.ln_eps, 0, 0, 0, s))) return rc;
+        if ((rc = GemmStep(T, D, w.qkvw, D, QKV, 3 * D, w.qkvb, Mi, 3 * D).run(ctx, s))) return rc;
         if ((rc = fp_attention_hd_fwd(QKV, 3 * D, AO, D, B, a.heads, v->head_dim, n_tok, npad, scale, s))) return rc;
-        if ((rc = gemm(AO, D, w.outw, D, R, D, w.outb, Mi, FP_EPI_BIAS_LS_RES, R))) return rc;
-        if ((rc = fp_layernorm(R, T, w.ln2w, w.ln2b, Mi, D, a.ln_eps, 0, 0, 0, s))) return rc;
-        if ((rc = gemm(T, D, w.fcw, D, H1, a.mlp_dim, w.fcb, Mi, FP_EPI_BIAS_GELU, nullptr))) return rc;
-        if ((rc = gemm(H1, a.mlp_dim, w.pjw, a.mlp_dim, R, D, w.pjb, Mi, FP_EPI_BIAS_LS_RES, R))) return rc;
+        if ((rc = fp_tower_out_proj(t, w, nullptr))) return rc;
+        if ((rc = fp_tower_mlp(t, w, nullptr, nullptr, nullptr, nullptr))) return rc;
     }
     // ---- ln_post on the class row of every crop, then the projection --------------------------------------------------------------------
     if ((rc = fp_layernorm(R, POOL, v->lnpostw, v->lnpostb, B, D, a.ln_eps, 1, npad, 0, s))) return rc;
-    if ((rc = gemm(POOL, D, v->projT, D, (bf16_t*)d_out, a.embed_dim, v->zeros, B, FP_EPI_BIAS, nullptr))) return rc;
-    return FP_OK;
+    return GemmStep(POOL, D, v->projT, D, (bf16_t*)d_out, a.embed_dim, v->zeros, B, a.embed_dim).run(ctx, s);
 }
 
 extern "C" double fp_clip_flops(const fp_clip* v, int B) {

@@ -14,6 +14,7 @@ struct fp_ctx {
     struct Buf { void* p = nullptr; size_t bytes = 0; };
     std::map<std::string, Buf> bufs;
     int get(const char* name, size_t bytes, void** out);
+    template <class T> int ws(const char* name, size_t bytes, T*& out) { return get(name, bytes, (void**)&out); }   // typed get
     // optional RCCL communicator (comm.hip: fp_comm_init); null = single rank
     void* comm = nullptr;
     int comm_rank = 0, comm_size = 1;
@@ -30,10 +31,18 @@ struct fp_ctx {
     static constexpr size_t SK_WS_BYTES = (size_t)64 << 20;
     static constexpr int SK_CNT_N = 16384;
     int sk_scratch(FpGemmArgs& g, hipStream_t s);   // lends the scratch to a launch (allocates on first use)
+    // THE launch path of every bf16 GEMM of the library: applies the context's options (gemm_row_split -> no_split), lends the
+    // balanced tier its scratch and calls fp_gemm_bf16
+    int gemm(FpGemmArgs& g, int epi, hipStream_t s);
     int* ffa_arrive = nullptr;   // per-crop arrival counters of the fused FFA launch (zero between calls: the last arriver resets its own)
     size_t total() const;
     void release();
 };
+// p = the context's workspace `name` of at least `bytes` (grown if needed), or return the error
+#define FP_WS(ctx, name, bytes, p)                                   \
+    do {                                                             \
+        if (int rc__ = (ctx)->ws(name, bytes, p)) return rc__;       \
+    } while (0)
 
 // attention.hip
 // log2(e) / sqrt(head_dim = 64): what the softmax multiplies q k^T by before exp2 — or what the q rows of the folded qkv weights carry
@@ -44,7 +53,8 @@ int fp_attention_fwd(const bf16_t* QK, int ldqk, const bf16_t* Vt, bf16_t* O, in
 int fp_attention_hd_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
                         hipStream_t stream);
 // vit_misc.hip
-int fp_im2col_norm(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps, int KP, hipStream_t s);
+// torchvision Normalize of the DINOv2 inputs (ImageNet); fp_im2col_norm_ms rounds mean / std to bf16 like its tensors in the image dtype
+constexpr float FP_IMAGENET_MEAN[3] = {0.485f, 0.456f, 0.406f}, FP_IMAGENET_SD[3] = {0.229f, 0.224f, 0.225f};
 int fp_im2col_norm_ms(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps, int KP, const float* mean, const float* sd, hipStream_t s);
 int fp_token_init(bf16_t* X, const bf16_t* cls, const bf16_t* pos0, const bf16_t* reg, int nreg, int B, int n_tok,
                   int npad, int D, hipStream_t s);

@@ -521,19 +521,8 @@ int fp_ln_fold(const bf16_t* W, const bf16_t* gamma, const bf16_t* beta, const b
     return FP_OK;
 }
 
-int fp_im2col_norm(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps, int KP, hipStream_t s) {
-    FP_REQUIRE(H % ps == 0 && W % ps == 0 && KP % 8 == 0 && KP >= 3 * ps * ps, "im2col: bad shape");
-    const long total = (long)B * (H / ps) * (W / ps) * (KP / 8);
-    const int blocks = (int)std::min<long>((total + 255) / 256, 256 * 16);
-    // torchvision Normalize builds mean/std tensors in the image dtype (bf16)
-    hipLaunchKernelGGL(im2col_norm_kernel, dim3(blocks), dim3(256), 0, s, img, A, B, H, W, ps, KP, rbf(0.485f),
-                       rbf(0.456f), rbf(0.406f), rbf(0.229f), rbf(0.224f), rbf(0.225f));
-    FP_LAUNCH_CHECK();
-    return FP_OK;
-}
-
-// the same kernel with the caller's per-channel mean / std (CLIP's constants: src/pipeline/retrieval/clip.py:12), rounded to bf16 here
-// like torchvision Normalize does on a bf16 tensor
+// normalise + unfold with the caller's per-channel mean / std (DINOv2: FP_IMAGENET_*, CLIP: src/pipeline/retrieval/clip.py:12), rounded to bf16
+// here like torchvision Normalize does on a bf16 tensor
 int fp_im2col_norm_ms(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps, int KP, const float* mean, const float* sd, hipStream_t s) {
     FP_REQUIRE(H % ps == 0 && W % ps == 0 && KP % 8 == 0 && KP >= 3 * ps * ps, "im2col: bad shape");
     const long total = (long)B * (H / ps) * (W / ps) * (KP / 8);

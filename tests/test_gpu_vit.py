@@ -29,7 +29,9 @@ def _metrics(got, ref):
 @pytest.mark.parametrize("model,H,layer,B", [("dinov2_vits14_reg", 224, 22, 2), ("dinov2_vitl14_reg", 420, 22, 2),
                                              ("dinov2_vitl14_reg", 518, 2, 1), ("dinov2_vits14_reg", 224, 5, 3),
                                              ("dinov2_vitl14_reg", 518, 22, 1),      # the bench / north-star configuration
-                                             ("dinov2_vitb14_reg", 518, 12, 1)])     # TrackingRefiner
+                                             ("dinov2_vitb14_reg", 518, 12, 1),      # TrackingRefiner
+                                             # 8704 rows: fc1 takes the big tile tier behind the stand-alone statistics kernel, qk the prologue
+                                             ("dinov2_vits14_reg", 224, 2, 32)])
 def test_vit_forward_vs_fp32_oracle(model, H, layer, B):
     from freepose_amd import ops
     from oracle import vit_ref
