@@ -5,6 +5,7 @@
 
 #include "../../include/freepose_hip.h"
 #include "tower_steps.h"
+#include "pnp_core.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -320,6 +321,30 @@ extern "C" int fp_depthmap_scale(fp_ctx* ctx, const double* d_depth, const uint8
     FP_WS(ctx, "scale.cnt", (size_t)n * 8 * sizeof(int), ws.cnt);
     return fp_depthmap_scale_launch(d_depth, d_masks, n, H, W, fx, fy, cx, cy, erosion_radius, std_factor, min_vertices, align, ws, d_scale,
                                     d_info, d_keep, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// TrackingRefiner correspondences and pose from tracks (refine.hip)
+extern "C" int fp_patch_points(fp_ctx* ctx, const double* d_samples, int S, const double* d_T, const double* d_K, const int32_t* d_cells,
+                               const int32_t* d_ncells, int B, int C, double patch, int32_t* d_out, void* stream) {
+    FP_REQUIRE(ctx && d_samples && d_T && d_K && d_cells && d_ncells && d_out, "patch_points: null argument");
+    FP_REQUIRE(S >= 1 && S <= (1 << 24), "patch_points: S=%d samples (1..2^24)", S);
+    FP_REQUIRE(B >= 0 && B <= 65535, "patch_points: B=%d items (0..65535 per call)", B);
+    FP_REQUIRE(C >= 0 && C <= (1 << 20), "patch_points: C=%d cells per item (0..2^20)", C);
+    FP_REQUIRE(patch > 0.0, "patch_points: patch %g (> 0)", patch);
+    if (B == 0 || C == 0) return FP_OK;
+    double* ws;
+    FP_WS(ctx, "refine.proj", (size_t)B * 4 * S * sizeof(double), ws);
+    return fp_patch_points_launch(d_samples, S, d_T, d_K, d_cells, d_ncells, B, C, patch, ws, d_out, (hipStream_t)stream);
+}
+
+extern "C" int fp_pnp_epnp(fp_ctx* ctx, const double* d_pts3d, const double* d_pts2d, const uint8_t* d_vis, const double* d_K9, int B, int N,
+                           double* d_out, void* stream) {
+    FP_REQUIRE(ctx && d_pts3d && d_pts2d && d_K9 && d_out, "pnp_epnp: null argument");
+    FP_REQUIRE(N >= FP_PNP_MIN_N && N <= FP_PNP_MAX_N, "pnp_epnp: N=%d points (%d..%d)", N, FP_PNP_MIN_N, FP_PNP_MAX_N);
+    FP_REQUIRE(B >= 0 && B <= (1 << 20), "pnp_epnp: B=%d problems (0..2^20 per call)", B);
+    if (B == 0) return FP_OK;
+    return fp_pnp_epnp_launch(d_pts3d, d_pts2d, d_vis, d_K9, B, N, d_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

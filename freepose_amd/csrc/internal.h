@@ -106,3 +106,8 @@ int fp_label_launch(const uint8_t* masks, int n, int H, int W, int connectivity,
 int fp_depthmap_scale_launch(const double* depth, const uint8_t* masks, int n, int H, int W, double fx, double fy, double cx, double cy,
                              double erosion_radius, double std_factor, int min_vertices, int align, const FpScaleWs& ws, double* scale,
                              int* info, uint8_t* keep, hipStream_t s);
+// refine.hip: TrackingRefiner correspondences and pose from tracks (pnp_core.h holds the host-checkable dense phases)
+int fp_patch_points_launch(const double* samples, int S, const double* Tm, const double* Km, const int* cells, const int* ncells, int B, int C,
+                           double patch, double* ws, int* out, hipStream_t s);   // ws: B * 4 * S doubles
+int fp_pnp_epnp_launch(const double* pts3d, const double* pts2d, const uint8_t* vis, const double* K9, int B, int N, double* out,
+                       hipStream_t s);

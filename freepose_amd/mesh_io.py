@@ -41,6 +41,24 @@ class TriMesh:
             self.vertices_f64 = self.vertices_f64 * s
         return self
 
+    def sample(self, n: int, seed=None) -> np.ndarray:
+        """n points [n,3] float64 on the surface: triangles drawn with probability proportional to their area, then uniform
+        barycentric coordinates (the square-root-free fold of the unit square), all from numpy.random.default_rng(seed) (or a
+        Generator passed as `seed`).  trimesh-compatible call (`mesh.sample(10000)`, tracking_refiner.py:103), but trimesh's own
+        random stream is NOT reproduced: the same surface distribution, other points."""
+        rng = seed if isinstance(seed, np.random.Generator) else np.random.default_rng(seed)
+        V = np.asarray(self.vertices_f64 if self.vertices_f64 is not None else self.vertices, dtype=np.float64)
+        F = np.asarray(self.faces, dtype=np.int64)
+        a, e1, e2 = V[F[:, 0]], V[F[:, 1]] - V[F[:, 0]], V[F[:, 2]] - V[F[:, 0]]
+        area = 0.5 * np.linalg.norm(np.cross(e1, e2), axis=1)
+        if not len(F) or not area.sum() > 0:
+            raise ValueError("TriMesh.sample: the mesh has no surface (no faces, or all of zero area)")
+        tri = rng.choice(len(F), size=int(n), p=area / area.sum())
+        uv = rng.random((int(n), 2))
+        fold = uv.sum(1) > 1.0
+        uv[fold] = 1.0 - uv[fold]
+        return a[tri] + uv[:, :1] * e1[tri] + uv[:, 1:] * e2[tri]
+
     def copy(self):
         c = lambda a: None if a is None else np.array(a, copy=True)   # noqa: E731
         return TriMesh(c(self.vertices), c(self.faces), c(self.vertex_colors), c(self.uv), c(self.texture), c(self.kd), c(self.vertices_f64))

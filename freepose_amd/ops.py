@@ -488,6 +488,67 @@ def depthmap_scales(depth, masks, K, erosion_radius: float = 8, std_factor: floa
     return (scales, info, keep) if return_keep else (scales, info)
 
 
+# ---- TrackingRefiner correspondences and pose from tracks (csrc/refine.hip) ------------------------------
+PNP_MIN_POINTS, PNP_MAX_POINTS = 4, 4096                   # csrc/pnp_core.h FP_PNP_MIN_N / FP_PNP_MAX_N
+PNP_OK, PNP_FEW, PNP_SINGULAR = 0, 1, 2
+
+
+def patch_points(samples, transforms, Ks, cells, ncells=None, patch: float = 14.0) -> torch.Tensor:
+    """TrackingRefiner._compute_3d_points (reference tracking_refiner.py:102-130) for B items in one call: samples f64 [S,3] (object frame,
+    shared), transforms f64 [B,4,4] object -> camera, Ks f64 [B,3,3] (or one [3,3] for all), cells i32 [B,C,2] (x, y) patch cells,
+    ncells i32 [B] real slots per item (default: all C) -> i32 [B,C] on the device: index of the sample chosen for each cell, -1 for a
+    cell no sample projects into and for slots >= ncells[b]."""
+    lib = _lib.load()
+    s = _dev(torch.as_tensor(samples), torch.float64)
+    T = _dev(torch.as_tensor(transforms), torch.float64)
+    K = _dev(torch.as_tensor(Ks), torch.float64)
+    c = _dev(torch.as_tensor(cells), torch.int32)
+    if s.dim() != 2 or s.shape[1] != 3 or s.shape[0] < 1:
+        raise ValueError(f"patch_points: samples {tuple(s.shape)} ([S,3], S >= 1)")
+    if T.dim() != 3 or tuple(T.shape[1:]) != (4, 4):
+        raise ValueError(f"patch_points: transforms {tuple(T.shape)} ([B,4,4])")
+    B = T.shape[0]
+    if K.dim() == 2:
+        K = K.unsqueeze(0).expand(B, 3, 3).contiguous()
+    if tuple(K.shape) != (B, 3, 3) or c.dim() != 3 or c.shape[0] != B or c.shape[2] != 2:
+        raise ValueError(f"patch_points: Ks {tuple(K.shape)} / cells {tuple(c.shape)} for B = {B} ([B,3,3] and [B,C,2])")
+    Cn = c.shape[1]
+    n = torch.full((B,), Cn, dtype=torch.int32, device=s.device) if ncells is None else _dev(torch.as_tensor(ncells), torch.int32)
+    if tuple(n.shape) != (B,):
+        raise ValueError(f"patch_points: ncells {tuple(n.shape)} ([B])")
+    out = torch.empty((B, Cn), dtype=torch.int32, device=s.device)
+    if B == 0 or Cn == 0:                                  # nothing to answer: an empty tensor has no address to pass
+        return out
+    check(lib.fp_patch_points(context(), ptr(s), s.shape[0], ptr(T), ptr(K), ptr(c), ptr(n), B, Cn, float(patch), ptr(out),
+                              current_stream()), "fp_patch_points")
+    return out
+
+
+def pnp_epnp(pts3d, pts2d, K, vis=None) -> torch.Tensor:
+    """cv2.solvePnP(..., flags=SOLVEPNP_EPNP) (reference tracking_refiner.py:173, smooth_poses_video.py:182) for the B frames of an
+    interval in one call: pts3d f64 [N,3] shared, pts2d f64 [B,N,2] (the tracker's pred_tracks), K [3,3], vis bool / u8 [B,N] or None
+    (all points used) -> f64 [B,16] on the device = R[9] row-major, t[3], mean reprojection error (px), used points, status (PNP_OK,
+    PNP_FEW: fewer than 4 used points, PNP_SINGULAR: coplanar or coincident points), 0.  R, t are NaN where the status is not 0."""
+    lib = _lib.load()
+    p3 = _dev(torch.as_tensor(pts3d), torch.float64)
+    p2 = _dev(torch.as_tensor(pts2d), torch.float64)
+    Kd = _dev(torch.as_tensor(K), torch.float64)
+    if p3.dim() != 2 or p3.shape[1] != 3 or p2.dim() != 3 or tuple(p2.shape[1:]) != (p3.shape[0], 2) or Kd.numel() != 9:
+        raise ValueError(f"pnp_epnp: pts3d {tuple(p3.shape)}, pts2d {tuple(p2.shape)}, K {tuple(Kd.shape)} ([N,3], [B,N,2], [3,3])")
+    B, N = p2.shape[0], p3.shape[0]
+    v = None
+    if vis is not None:
+        v = _dev(torch.as_tensor(vis))
+        v = _dev(v != 0, torch.uint8)
+        if tuple(v.shape) != (B, N):
+            raise ValueError(f"pnp_epnp: vis {tuple(v.shape)} ([B,N] = {(B, N)})")
+    out = torch.empty((B, 16), dtype=torch.float64, device=p3.device)
+    if B == 0:                                             # no problem: an empty tensor has no address to pass
+        return out
+    check(lib.fp_pnp_epnp(context(), ptr(p3), ptr(p2), ptr(v), ptr(Kd), B, N, ptr(out), current_stream()), "fp_pnp_epnp")
+    return out
+
+
 # ---- pose-error evaluation (csrc/eval.hip) ----------------------------------------------------------
 EVAL_XF_LD, EVAL_TABLE_LD, EVAL_MAX_TAUS = 40, 8, 16      # csrc/internal.h FP_EVAL_*
 EVAL_MAX_PAIRS = 65535                                     # pairs per launch (grid z / y)

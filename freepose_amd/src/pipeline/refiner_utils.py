@@ -119,3 +119,44 @@ def cubic_resize(img: np.ndarray, dsize) -> np.ndarray:
     rows = (src[:, ix] * cx[None, :, :]).sum(-1, dtype=np.float32)          # [H, dw]
     out = (rows[iy, :] * cy[:, :, None]).sum(1, dtype=np.float32)           # [dh, dw]
     return out.astype(np.float32)
+
+
+# ---- trajectory smoothing (reference refiner_utils.py:173-221): host numpy / scipy, once per clip ----------------------------------------
+def average_quaternions(Q: np.ndarray) -> np.ndarray:
+    """the quaternion (x, y, z, w) that best represents the rows of Q [M,4]: the principal eigenvector of the mean outer product
+    (1 / M) sum q q^T, which does not care about the sign of any q.  The returned vector's own sign is the eigen-solver's choice
+    (the reference takes numpy.linalg.eig's; this one numpy.linalg.eigh's): as a rotation it is the same."""
+    quats = np.asarray(Q, dtype=np.float64).reshape(-1, 4)
+    second_moment = quats.T @ quats / len(quats)
+    _, vecs = np.linalg.eigh(second_moment)         # ascending eigenvalues: the last column belongs to the largest
+    return vecs[:, -1]
+
+
+def moving_average(data, window_size=5, fun=np.mean):
+    """row i of the result = fun(rows i - w // 2 .. i + w // 2 of data), the window cut off at both ends of the sequence; the
+    result has data's shape and dtype"""
+    data = np.asarray(data)
+    reach = window_size // 2
+    if len(data) == 0:
+        return data.copy()
+    return np.stack([np.asarray(fun(data[max(i - reach, 0):i + reach + 1])) for i in range(len(data))]).astype(data.dtype).reshape(data.shape)
+
+
+def smooth_quaternions(data, window_size=5):
+    """every quaternion replaced by average_quaternions of its window"""
+    return moving_average(data, window_size, average_quaternions)
+
+
+def smooth_3dvec(data, window_size=5):
+    """every vector replaced by the mean of its window"""
+    return moving_average(data, window_size, lambda rows: rows.mean(axis=0))
+
+
+def smooth_transforms(TCOs: np.ndarray) -> np.ndarray:
+    """[n,4,4] poses -> the same trajectory with translations averaged over a window of 5 and rotations over a window of 9"""
+    from scipy.spatial.transform import Rotation
+    poses = np.array(TCOs, dtype=np.float64, copy=True)
+    poses[:, :3, 3] = smooth_3dvec(poses[:, :3, 3].copy(), window_size=5)
+    as_quats = Rotation.from_matrix(poses[:, :3, :3]).as_quat()
+    poses[:, :3, :3] = Rotation.from_quat(smooth_quaternions(as_quats, window_size=9)).as_matrix()
+    return poses

@@ -369,6 +369,33 @@ double fp_clip_flops(const fp_clip* clip, int B);
 int fp_knn_l2(fp_ctx* ctx, const float* d_table, int N, int E, const float* d_queries, int Q, int k, int32_t* d_out_idx, float* d_out_d2,
               void* stream);
 
+/* ---- f-3b: TrackingRefiner correspondences and pose from tracks ------------------------------------------ */
+/* TrackingRefiner._compute_3d_points (src/pipeline/estimators/tracking_refiner.py:102-130), batched: which surface sample stands for each
+ * patch cell.  d_samples f64 [S,3] object-frame surface samples shared by the B items, d_T f64 [B,16] row-major object -> camera
+ * transforms, d_K f64 [B,9], d_cells i32 [B,C,2] the (x, y) patch cells to answer, d_ncells i32 [B] how many of an item's C slots are
+ * real -> d_out i32 [B,C]: index of the chosen sample, -1 for a cell no sample projects into and for slots >= d_ncells[b].
+ * Per sample, fp64 in this order: Xc = ((T00 x + T01 y) + T02 z) + T03 (Yc, Zc likewise), u' = (K00 Xc + K01 Yc) + K02 Zc (v', w'
+ * likewise), u = u'/w', v = v'/w', cell = (floor(u/patch), floor(v/patch)), d2 = (u/patch - floor(u/patch) - 0.5)^2 + (v/patch -
+ * floor(v/patch) - 0.5)^2; a sample with non-finite u or v belongs to no cell.  Of a cell's m members the q = ceil(0.25 m) smallest by
+ * (d2, sample index) are kept, and of those the minimum by (Zc, d2, sample index) is returned (the reference's argsort -> [:ceil] ->
+ * argmin).  Exact selection, no floating-point atomics: two calls give the same bits.  1 <= S <= 2^24, B <= 65535, C <= 2^20. */
+int fp_patch_points(fp_ctx* ctx, const double* d_samples, int S, const double* d_T, const double* d_K, const int32_t* d_cells,
+                    const int32_t* d_ncells, int B, int C, double patch, int32_t* d_out, void* stream);
+/* cv2.solvePnP(p3d, p2d, K, [], flags=SOLVEPNP_EPNP) as called at tracking_refiner.py:173 and scripts/smooth_poses_video.py:182, for all
+ * frames of an interval in one call.  d_pts3d f64 [N,3] shared by the B problems, d_pts2d f64 [B,N,2] (the layout of the tracker's
+ * pred_tracks), d_vis u8 [B,N] or NULL (non-zero = the point is used), d_K9 f64 [9] (fx, cx, fy, cy are read: no skew), 4 <= N <= 4096
+ * -> d_out f64 [B,16] = {R[9] row-major, t[3], mean reprojection error in pixels over the used points, number of used points,
+ * status, 0}.  status 0: solved; 1: fewer than 4 used points; 2: the control-point basis is singular (coplanar or coincident points:
+ * the smallest eigenvalue of the 3x3 scatter is <= 1e-12 x the largest).  With a non-zero status R, t and the error are NaN and the
+ * call still returns FP_OK; such a problem does not disturb its neighbours in the batch.
+ * EPnP (Lepetit, Moreno-Noguer, Fua, IJCV 2009) in the variant OpenCV ships, restated (not pinned to OpenCV): image points normalised
+ * with K first, control points = centroid + principal axes scaled by sqrt(lambda/n), barycentrics, M^T M over the used points, the
+ * eigenvectors of its four smallest eigenvalues, the 6x10 system, three beta initialisations, five Gauss-Newton steps each, sign by
+ * positive mean depth, Horn's absolute orientation (3x3 SVD, determinant corrected), the candidate with the smallest mean
+ * reprojection error.  All fp64; sums over points are reductions in a fixed tree order: two calls give the same bits. */
+int fp_pnp_epnp(fp_ctx* ctx, const double* d_pts3d, const double* d_pts2d, const uint8_t* d_vis, const double* d_K9, int B, int N,
+                double* d_out, void* stream);
+
 /* ---- measurement helpers (bench.py: HIP-event timing on the launch stream) ----------------------------- */
 int fp_timer_create(void** out);
 int fp_timer_start(void* timer, void* stream);
