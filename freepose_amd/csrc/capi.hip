@@ -6,6 +6,7 @@
 #include "../../include/freepose_hip.h"
 #include "tower_steps.h"
 #include "pnp_core.h"
+#include "video_eval_core.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -345,6 +346,45 @@ extern "C" int fp_pnp_epnp(fp_ctx* ctx, const double* d_pts3d, const double* d_p
     FP_REQUIRE(B >= 0 && B <= (1 << 20), "pnp_epnp: B=%d problems (0..2^20 per call)", B);
     if (B == 0) return FP_OK;
     return fp_pnp_epnp_launch(d_pts3d, d_pts2d, d_vis, d_K9, B, N, d_out, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// video velocity errors (video_eval.hip).  The per-track tables come from the host: every limit is checked here, before anything is
+// launched, and the tables are then copied into the context's workspace in stream order.
+extern "C" int fp_video_errors(fp_ctx* ctx, const double* d_est, const double* d_gt, const int32_t* h_meta, const double* h_params, int M,
+                               int V, int Nmax, int D, double* d_per_offset, double* d_final, double* d_aligned, double* d_pairs,
+                               void* stream) {
+    FP_REQUIRE(ctx && d_est && d_gt && h_meta && h_params && d_per_offset && d_final, "video_errors: null argument");
+    FP_REQUIRE(M >= 0 && M <= 65535, "video_errors: M=%d tracks (0..65535 per call)", M);
+    FP_REQUIRE(V >= 1 && V <= (1 << 20), "video_errors: V=%d ground-truth trajectories (1..2^20)", V);
+    FP_REQUIRE(Nmax >= FP_VE_MIN_N && Nmax <= (1 << 20), "video_errors: Nmax=%d frames (%d..2^20)", Nmax, FP_VE_MIN_N);
+    FP_REQUIRE(D >= 1 && D <= FP_VE_MAX_D, "video_errors: D=%d time offsets (1..%d)", D, FP_VE_MAX_D);
+    for (int m = 0; m < M; ++m) {
+        const int32_t* mt = h_meta + (size_t)m * FP_VE_META_LD;
+        const double* pr = h_params + (size_t)m * FP_VE_PARAM_LD;
+        FP_REQUIRE(mt[0] >= 0 && mt[0] < V, "video_errors: track %d: video %d (0..%d)", m, mt[0], V - 1);
+        FP_REQUIRE(mt[1] >= FP_VE_MIN_N && mt[1] <= Nmax, "video_errors: track %d: N=%d frames (%d..Nmax=%d)", m, mt[1], FP_VE_MIN_N, Nmax);
+        FP_REQUIRE(mt[2] >= 1 && mt[2] <= FP_VE_MAX_SYM, "video_errors: track %d: n_sym=%d (1..%d)", m, mt[2], FP_VE_MAX_SYM);
+        FP_REQUIRE((mt[3] & ~(FP_VE_HAS_AXIS | FP_VE_HAS_K | FP_VE_NO_ALIGN)) == 0, "video_errors: track %d: flags %d", m, mt[3]);
+        for (int d = 0; d < D; ++d)
+            FP_REQUIRE(mt[4 + d] >= 1 && mt[4 + d] <= mt[1] - 1, "video_errors: track %d: dt[%d]=%d (1..N-1=%d)", m, d, mt[4 + d], mt[1] - 1);
+        FP_REQUIRE(pr[0] > 0.0 && pr[1] > 0.0 && pr[0] < INFINITY && pr[1] < INFINITY, "video_errors: track %d: scales %g, %g (finite, > 0)",
+                   m, pr[0], pr[1]);
+        FP_REQUIRE(pr[2] > 0.0 && pr[3] > 0.0 && pr[2] < INFINITY && pr[3] < INFINITY, "video_errors: track %d: frame size %g x %g", m, pr[2],
+                   pr[3]);
+    }
+    if (M == 0) return FP_OK;
+    int32_t* meta;
+    double *params, *frames, *aligned = d_aligned;
+    FP_WS(ctx, "video.meta", (size_t)M * FP_VE_META_LD * sizeof(int32_t), meta);
+    FP_WS(ctx, "video.params", (size_t)M * FP_VE_PARAM_LD * sizeof(double), params);
+    FP_WS(ctx, "video.frames", (size_t)M * Nmax * FP_VE_FRAME_LD * sizeof(double), frames);
+    if (!aligned) FP_WS(ctx, "video.aligned", (size_t)M * Nmax * 3 * sizeof(double), aligned);
+    hipStream_t s = (hipStream_t)stream;
+    FP_HIP(hipMemcpyAsync(meta, h_meta, (size_t)M * FP_VE_META_LD * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    FP_HIP(hipMemcpyAsync(params, h_params, (size_t)M * FP_VE_PARAM_LD * sizeof(double), hipMemcpyHostToDevice, s));
+    FP_HIP(hipStreamSynchronize(s));                       // the host tables are the caller's again when this entry returns
+    return fp_video_errors_launch(d_est, d_gt, meta, params, M, Nmax, D, aligned, frames, d_per_offset, d_final, d_pairs, s);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -111,3 +111,7 @@ int fp_patch_points_launch(const double* samples, int S, const double* Tm, const
                            double patch, double* ws, int* out, hipStream_t s);   // ws: B * 4 * S doubles
 int fp_pnp_epnp_launch(const double* pts3d, const double* pts2d, const uint8_t* vis, const double* K9, int B, int N, double* out,
                        hipStream_t s);
+// video_eval.hip: video velocity errors (video_eval_core.h holds the host-checkable arithmetic).  meta / params are the device copies of
+// fp_video_errors' host tables; aligned [M,Nmax,3], frames [M,Nmax,FP_VE_FRAME_LD]; pairs_out may be null
+int fp_video_errors_launch(const double* est, const double* gt, const int* meta, const double* params, int M, int Nmax, int D,
+                           double* aligned, double* frames, double* per_offset, double* final_out, double* pairs_out, hipStream_t s);

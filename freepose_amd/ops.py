@@ -549,6 +549,106 @@ def pnp_epnp(pts3d, pts2d, K, vis=None) -> torch.Tensor:
     return out
 
 
+# ---- video velocity errors (csrc/video_eval.hip) ----------------------------------------------------
+VIDEO_META_LD, VIDEO_PARAM_LD = 20, 16                     # csrc/video_eval_core.h FP_VE_META_LD / FP_VE_PARAM_LD
+VIDEO_MAX_OFFSETS, VIDEO_MAX_SYM, VIDEO_MAX_TRACKS = 16, 1024, 65535
+VIDEO_HAS_AXIS, VIDEO_HAS_K, VIDEO_NO_ALIGN = 1, 2, 4
+
+
+def _pose_rows(x, what) -> torch.Tensor:
+    """[B,N,4,4] poses (or [B,N,12] = R[9] row-major, t[3]) -> f64 [B,N,12] on the device"""
+    p = _dev(torch.as_tensor(x), torch.float64)
+    if p.dim() == 4 and tuple(p.shape[2:]) == (4, 4):
+        p = torch.cat([p[:, :, :3, :3].reshape(p.shape[0], p.shape[1], 9), p[:, :, :3, 3]], dim=2).contiguous()
+    if p.dim() != 3 or p.shape[2] != 12:
+        raise ValueError(f"video_errors: {what} {tuple(p.shape)} ([B,N,4,4] or [B,N,12])")
+    return p
+
+
+def _per_track(x, M, what, dtype, tail=()):
+    a = np.asarray(x, dtype=dtype)
+    if a.shape == tuple(tail):
+        a = np.broadcast_to(a, (M,) + tuple(tail))
+    if a.shape != (M,) + tuple(tail):
+        raise ValueError(f"video_errors: {what} {a.shape} (one per track: {(M,) + tuple(tail)})")
+    return a
+
+
+def video_errors(est, gt, dts, est_scale, gt_scale, w, h, video=None, n_frames=None, sym_axis=None, n_sym=101, K=None,
+                 align: bool = True, return_aligned: bool = False, return_pairs: bool = False):
+    """The velocity errors of the reference's src/utils/video_evaluation.py (get_average_rot / proj / depth_errors_dt :4-34 with
+    get_rot_errors :37-63, get_translation_errors_depth / _proj :66-109, align_object_origins :112-155) for M tracks against V ground-truth
+    trajectories in one call: est f64 [M,Nmax,4,4] (or [M,Nmax,12] = R[9] row-major, t[3]) estimated poses, gt [V,Nmax,4,4] likewise, dts
+    int [M,D] time offsets (D <= 16, 1 <= dt <= N - 1), est_scale / gt_scale / w / h one number or [M], video int [M] row of gt a track
+    is scored against (default: its own index, V == M), n_frames int [M] length N >= 2 of each track (default Nmax; rows past it are
+    padding), sym_axis None, one 3-vector for all, or M entries of None / 3-vector (used as given, not normalised), n_sym the symmetry
+    grid linspace(-pi, pi, n_sym), 1..1024, K None, one [3,3], or M entries of None / [3,3] (None: f = sqrt(w^2 + h^2), c = (w/2, h/2))
+    -> (per_offset f64 [M,D,3], final f64 [M,3]) on the device: per offset the mean over the N - dt pairs / dt of (rot, proj, depth);
+    final = mean over the offsets with rot in degrees and proj / sqrt(w^2 + h^2) * 100 (eval_videos.py:195-205).  align=False scores
+    the translations as given (no origin alignment: get_translation_errors_* called on their own).  return_aligned adds
+    f64 [M,Nmax,3], the estimates' translations at the aligned object origin; return_pairs adds f64 [M,D,Nmax,3], the per-pair errors
+    (NaN at t1 >= N - dt).  Fixed summation order, no atomics: two calls give the same bits."""
+    lib = _lib.load()
+    e, g = _pose_rows(est, "est"), _pose_rows(gt, "gt")
+    M, Nmax, V = e.shape[0], e.shape[1], g.shape[0]
+    if g.shape[1] != Nmax:
+        raise ValueError(f"video_errors: gt {tuple(g.shape)} for est {tuple(e.shape)} (the same Nmax)")
+    d = np.asarray(dts)
+    if d.ndim == 1:
+        d = np.broadcast_to(d, (M, len(d)))
+    if d.ndim != 2 or d.shape[0] != M or not 1 <= d.shape[1] <= VIDEO_MAX_OFFSETS or not np.issubdtype(d.dtype, np.integer):
+        raise ValueError(f"video_errors: dts {d.shape} {d.dtype} (int [M,D] = [{M}, 1..{VIDEO_MAX_OFFSETS}])")
+    D = d.shape[1]
+    if video is None and V != M:
+        raise ValueError(f"video_errors: {M} tracks, {V} ground-truth trajectories and no `video`")
+    meta = np.zeros((M, VIDEO_META_LD), np.int32)
+    params = np.zeros((M, VIDEO_PARAM_LD), np.float64)
+    meta[:, 0] = np.arange(M) if video is None else _per_track(video, M, "video", np.int64)
+    meta[:, 1] = Nmax if n_frames is None else _per_track(n_frames, M, "n_frames", np.int64)
+    meta[:, 2] = _per_track(n_sym, M, "n_sym", np.int64)
+    meta[:, 4:4 + D] = d
+    meta[:, 3] = 0 if align else VIDEO_NO_ALIGN
+    for col, (x, what) in enumerate(((est_scale, "est_scale"), (gt_scale, "gt_scale"), (w, "w"), (h, "h"))):
+        params[:, col] = _per_track(x, M, what, np.float64)
+    def entries(x, shape):                                 # None, one value for all, or one (None or value) per track
+        if x is None:
+            return [None] * M
+        if not any(v is None for v in x) and np.shape(x) == shape:
+            return [x] * M
+        return list(x)
+    axes, Ks = entries(sym_axis, (3,)), entries(K, (3, 3))
+    if len(axes) != M or len(Ks) != M:
+        raise ValueError(f"video_errors: {len(axes)} sym_axis / {len(Ks)} K entries for {M} tracks")
+    for m in range(M):
+        if axes[m] is not None:
+            a = np.asarray(axes[m], dtype=np.float64)
+            if a.shape != (3,):
+                raise ValueError(f"video_errors: sym_axis of track {m} {a.shape} ([3])")
+            meta[m, 3] |= VIDEO_HAS_AXIS
+            params[m, 4:7] = a
+        if Ks[m] is not None:
+            k = np.asarray(Ks[m], dtype=np.float64)
+            if k.shape != (3, 3):
+                raise ValueError(f"video_errors: K of track {m} {k.shape} ([3,3])")
+            meta[m, 3] |= VIDEO_HAS_K
+            params[m, 7:16] = k.ravel()
+    if M > VIDEO_MAX_TRACKS:
+        raise ValueError(f"video_errors: {M} tracks (at most {VIDEO_MAX_TRACKS} per call)")
+    per = torch.empty((M, D, 3), dtype=torch.float64, device=e.device)
+    fin = torch.empty((M, 3), dtype=torch.float64, device=e.device)
+    aligned = torch.zeros((M, Nmax, 3), dtype=torch.float64, device=e.device) if return_aligned else None
+    pairs = torch.full((M, D, Nmax, 3), float("nan"), dtype=torch.float64, device=e.device) if return_pairs else None
+    if M > 0:                                              # no track: an empty tensor has no address to pass
+        check(lib.fp_video_errors(context(), ptr(e), ptr(g), ptr(meta), ptr(params), M, V, Nmax, D, ptr(per), ptr(fin), ptr(aligned),
+                                  ptr(pairs), current_stream()), "fp_video_errors")
+    out = (per, fin)
+    if return_aligned:
+        out += (aligned,)
+    if return_pairs:
+        out += (pairs,)
+    return out
+
+
 # ---- pose-error evaluation (csrc/eval.hip) ----------------------------------------------------------
 EVAL_XF_LD, EVAL_TABLE_LD, EVAL_MAX_TAUS = 40, 8, 16      # csrc/internal.h FP_EVAL_*
 EVAL_MAX_PAIRS = 65535                                     # pairs per launch (grid z / y)

@@ -396,6 +396,35 @@ int fp_patch_points(fp_ctx* ctx, const double* d_samples, int S, const double* d
 int fp_pnp_epnp(fp_ctx* ctx, const double* d_pts3d, const double* d_pts2d, const uint8_t* d_vis, const double* d_K9, int B, int N,
                 double* d_out, void* stream);
 
+/* ---- video evaluation: velocity errors of pose tracks ------------------------------------------------------ */
+/* The scorer of scripts/eval_videos.py:186-208, i.e. src/utils/video_evaluation.py: get_average_rot_errors_dt (:4-11, get_rot_errors and
+ * rot_error_in_cframe :37-63), get_average_proj_errors_dt (:25-34, get_translation_errors_proj and project :80-109),
+ * get_average_depth_errors_dt (:14-22, get_translation_errors_depth :66-77) and align_object_origins / change_object_origin (:112-155),
+ * for M tracks against V ground-truth trajectories in one call.
+ * d_est f64 [M,Nmax,12] and d_gt f64 [V,Nmax,12]: per frame R[9] row-major then t[3]; rows past a track's own length are not read.
+ * HOST tables (checked before anything is launched, copied before the call returns):
+ *   h_meta   i32 [M,20] = {video (row of d_gt), n_frames N, n_sym, flags, dt[16]}; flags bit 0: sym_axis is given (otherwise S = I and
+ *            n_sym is not used), bit 1: K is given (otherwise f = sqrt(w^2 + h^2), c = (w/2, h/2)), bit 2: no origin alignment (the
+ *            translations are scored as given); only dt[0..D) are read
+ *   h_params f64 [M,16] = {est_scale, gt_scale, w, h, sym_axis[3], K[9]}
+ * Limits, refused with FP_ERR_INVALID and a message: 2 <= N <= Nmax, 1 <= dt <= N - 1, 1 <= D <= 16, 1 <= n_sym <= 1024, M <= 65535,
+ * scales and frame size finite and > 0.
+ * Per pair (t1, t2 = t1 + dt), all fp64:
+ *   rot   = min over S of |log(R2e R1e^T) - log((R2g S) R1g^T)|, S = exp(sym_axis * a), a = linspace(-pi, pi, n_sym) (the axis is used
+ *           as given, not normalised); log: angle atan2(|v|, (tr - 1) / 2) in [0, pi], a series below 1e-3, the axis from the symmetric
+ *           part above pi - 1e-2 (csrc/video_eval_core.h)
+ *   proj  = |(pi(t2e) - pi(t1e)) - (pi(t2g) - pi(t1g))|, pi(x) = (K x)[:2] / (K x)[2]
+ *   depth = |(|t1e| / s_e - |t2e| / s_e) - (|t1g| / s_g - |t2g| / s_g)|
+ * where the estimate's translations in proj and depth are first moved to the aligned object origin: per frame x = t_g / |t_g| * |t_e|,
+ * o = R_e^T (x - t_e), kept when |o| < est_scale; the mean of the kept o, its length limited to est_scale / 2; t_e <- R_e o + t_e (no
+ * frame kept: unchanged).
+ * -> d_per_offset f64 [M,D,3]: mean over the N - dt pairs / dt, for (rot, proj, depth); d_final f64 [M,3]: the mean over the D offsets,
+ * rot in degrees, proj / sqrt(w^2 + h^2) * 100.  Optional (NULL = not wanted): d_aligned f64 [M,Nmax,3] the moved translations,
+ * d_pairs f64 [M,D,Nmax,3] the per-pair errors (rows t1 >= N - dt are left as they are).
+ * No floating-point atomics, every sum in a fixed order: two calls give the same bits. */
+int fp_video_errors(fp_ctx* ctx, const double* d_est, const double* d_gt, const int32_t* h_meta, const double* h_params, int M, int V,
+                    int Nmax, int D, double* d_per_offset, double* d_final, double* d_aligned, double* d_pairs, void* stream);
+
 /* ---- measurement helpers (bench.py: HIP-event timing on the launch stream) ----------------------------- */
 int fp_timer_create(void** out);
 int fp_timer_start(void* timer, void* stream);

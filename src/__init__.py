@@ -5,7 +5,7 @@ import importlib
 import sys
 
 _ALIASES = [
-    "utils", "utils.bbox_utils", "pipeline", "pipeline.utils", "pipeline.retrieval", "pipeline.retrieval.dino", "pipeline.retrieval.clip",
+    "utils", "utils.bbox_utils", "utils.video_evaluation", "pipeline", "pipeline.utils", "pipeline.retrieval", "pipeline.retrieval.dino", "pipeline.retrieval.clip",
     "pipeline.retrieval.renderer", "pipeline.estimators", "pipeline.estimators.pose_estimator",
     "pipeline.estimators.online_pose_estimator", "pipeline.estimators.tracking_refiner", "pipeline.estimators.scale_estimators",
     "pipeline.refiner_utils",
