@@ -134,6 +134,25 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, lane_xor<1>(v));
     return v;
 }
+// the same butterflies on integers (counts and maxima of the top-k select)
+__device__ __forceinline__ int wave_sum_i(int v) {
+    v += __float_as_int(lane_xor<32>(__int_as_float(v)));
+    v += __float_as_int(lane_xor<16>(__int_as_float(v)));
+    v += __float_as_int(lane_xor<8>(__int_as_float(v)));
+    v += __float_as_int(lane_xor<4>(__int_as_float(v)));
+    v += __float_as_int(lane_xor<2>(__int_as_float(v)));
+    v += __float_as_int(lane_xor<1>(__int_as_float(v)));
+    return v;
+}
+__device__ __forceinline__ int wave_max_i(int v) {
+    v = max(v, __float_as_int(lane_xor<32>(__int_as_float(v))));
+    v = max(v, __float_as_int(lane_xor<16>(__int_as_float(v))));
+    v = max(v, __float_as_int(lane_xor<8>(__int_as_float(v))));
+    v = max(v, __float_as_int(lane_xor<4>(__int_as_float(v))));
+    v = max(v, __float_as_int(lane_xor<2>(__int_as_float(v))));
+    v = max(v, __float_as_int(lane_xor<1>(__int_as_float(v))));
+    return v;
+}
 
 // async global -> LDS copy, 16 B per lane, LDS image is lane-linear from the wave-uniform base
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {

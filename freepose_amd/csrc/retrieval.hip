@@ -1,14 +1,8 @@
 // Retrieval kernels (K10, K12, K13 of SURVEY.md §2.3), gfx950 only.  All HBM-bound byte/row streaming:
 // coalesced 16-byte loads, one wave per row, wave-shuffle reductions, no MFMA.
-//
-// Canonical arithmetic ("dot64"), shared with oracle/fp_oracle.c so indices AND scores are bit-exact:
-//   lane l (0..63) owns elements (c*64 + l)*8 + e  (c = 0.., e = 0..7) of the D-vector,
-//   p_l = fmaf chain over (c, e) ascending; s = xor-butterfly sum over offsets 32,16,8,4,2,1;
-//   score = bf16_rne(s)  (the reference rounds bank@feature to bf16 before .float()/topk:
-//   scripts/extract_proposals_ground.py:137-140).
-// Ordering for top-k: score descending, then index ascending (torch.topk's tie order is unspecified;
-// this is the documented canonical rule).
+// The canonical "dot64" arithmetic and the (score desc, index asc) order they share with oracle/fp_oracle.c: dot64.h.
 #include "internal.h"
+#include "dot64.h"
 
 #include <stdlib.h>
 
@@ -51,12 +45,7 @@ __global__ __launch_bounds__(256) void bank_scan_kernel(const bf16_t* __restrict
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             if (r0 + u >= r_end) break;      // wave-uniform: rows past the run are neither fetched nor stored
-            const int r = r0 + u;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int base = (c * 64 + lane) * 8;
-                dst[u][c] = (FULL || base < D) ? *(const uint4*)(bank + (size_t)r * D + base) : make_uint4(0, 0, 0, 0);
-            }
+            d64_load<NCH, FULL>(dst[u], bank, (size_t)(r0 + u) * D, D, lane);
         }
     };
     auto reduce_chunk = [&](const uint4 (&raw)[RU][NCH], int r0) {
@@ -67,6 +56,8 @@ __global__ __launch_bounds__(256) void bank_scan_kernel(const bf16_t* __restrict
             for (int q = 0; q < QT; ++q) acc[u][q] = 0.f;
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
+                // d64_dot's chain, one word (two steps) of each of the QT queries at a time: the words are unpacked as they are
+                // consumed (unpacking the slot first, as d64_unpack does, made the compiler wait for a chunk right behind its fetch)
                 const uint32_t w[4] = {raw[u][c].x, raw[u][c].y, raw[u][c].z, raw[u][c].w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -96,16 +87,14 @@ __global__ __launch_bounds__(256) void bank_scan_kernel(const bf16_t* __restrict
     if (r_begin < r_end) fetch(bufA, r_begin);
     if (r_begin + RU < r_end) fetch(bufB, r_begin + RU);
 #pragma unroll
-    for (int q = 0; q < QT; ++q)
+    for (int q = 0; q < QT; ++q) {
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int base = (c * 64 + lane) * 8;
-            const bool ok = (q_begin + q < Q) && (FULL || base < D);
-            const uint4 qw = ok ? *(const uint4*)(queries + (size_t)(q_begin + q) * D + base) : make_uint4(0, 0, 0, 0);
-            const uint32_t w[4] = {qw.x, qw.y, qw.z, qw.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { qv[q][c][2 * e] = lo_bf(w[e]); qv[q][c][2 * e + 1] = hi_bf(w[e]); }
+        for (int c = 0; c < NCH; ++c) {      // chunk by chunk: each is unpacked where it is loaded
+            uint4 qw;
+            d64_load_chunk<FULL>(qw, queries, (size_t)(q_begin + q) * D, c, D, lane, q_begin + q < Q);
+            d64_unpack(qw, qv[q][c]);
         }
+    }
     for (int r0 = r_begin; r0 < r_end; r0 += 2 * RU) {
         if (r0 != r_begin && r0 + RU < r_end) fetch(bufB, r0 + RU);
         reduce_chunk(bufA, r0);
@@ -145,6 +134,62 @@ __device__ __forceinline__ int block_excl_scan(int v, int* sh, int& total) {
     total = (int)tot;
     __syncthreads();
     return (int)(base + x - (unsigned)v);
+}
+
+// ---- candidates: (key desc, index asc) as ONE descending order of distinct 64-bit composites ------------------------------------
+// high word = key, low word = cand_flip(index): a smaller index is a larger composite; the flip is its own inverse (pack and decode)
+__device__ __forceinline__ int cand_flip(int i) { return 0x7fffffff - i; }
+__device__ __forceinline__ unsigned long long cand_pack(uint32_t key, int i) {
+    return ((unsigned long long)key << 32) | (unsigned)cand_flip(i);
+}
+__device__ __forceinline__ int cand_index(unsigned long long c) { return cand_flip((int)(unsigned)(c & 0xffffffffu)); }
+// candidate c of query q is the rank-th best: its score (16-bit key) and bank row
+__device__ __forceinline__ void cand_emit(unsigned long long c, int q, int k, int rank, int idx_offset, float* out_scores,
+                                          int* out_idx) {
+    out_scores[(size_t)q * k + rank] = key16_to_float((uint32_t)(c >> 32));
+    out_idx[(size_t)q * k + rank] = idx_offset + cand_index(c);
+}
+// one key of the ordered compaction (index order): all keys > T take slots [0, ngt), the first need_eq keys == T the slots after them
+__device__ __forceinline__ void cand_place(unsigned long long* cand, int key, int i, int T, int ngt, int need_eq, int& og, int& oe) {
+    if (key > T) cand[og++] = cand_pack(key, i);
+    else if (key == T) { if (oe < need_eq) cand[ngt + oe] = cand_pack(key, i); ++oe; }
+}
+// in-place bitonic sort of a[0, n2) in LDS, descending; n2 a power of two; ends on a barrier
+template <typename T>
+__device__ __forceinline__ void lds_bitonic_desc(T* a, int n2, int tid, int nthreads) {
+    for (int size = 2; size <= n2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < n2; i += nthreads) {
+                const int j = i ^ stride;
+                if (j > i) {
+                    const bool desc = ((i & size) == 0);
+                    const T x = a[i], y = a[j];
+                    if ((x < y) == desc) { a[i] = y; a[j] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+// the k survivors of a select: pad to a power of two, sort, emit in order
+__device__ __forceinline__ void cand_sort_emit(unsigned long long* cand, int q, int k, int tid, int idx_offset, float* out_scores,
+                                               int* out_idx) {
+    int n2 = 1;
+    while (n2 < k) n2 <<= 1;
+    for (int i = k + tid; i < n2; i += SEL_T) cand[i] = 0ull;
+    __syncthreads();
+    lds_bitonic_desc(cand, n2, tid, SEL_T);
+    for (int i = tid; i < k; i += SEL_T) cand_emit(cand[i], q, k, i, idx_offset, out_scores, out_idx);
+}
+// rank sort of n <= SEL_T candidates: they are distinct 64-bit values, so a candidate's rank is the number of larger ones (broadcast
+// LDS reads); the best k are emitted
+__device__ __forceinline__ void rank_sort_emit(const unsigned long long* cand, int n, int q, int k, int tid, int idx_offset,
+                                               float* out_scores, int* out_idx) {
+    if (tid < n) {
+        const unsigned long long mine = cand[tid];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += cand[j] > mine;
+        if (rank < k) cand_emit(mine, q, k, rank, idx_offset, out_scores, out_idx);
+    }
 }
 
 // LDSKEYS: the query's whole key row (N x 2 B; 92 KB for the 46 037-row bank) is staged into LDS once with coalesced loads
@@ -202,33 +247,9 @@ __global__ __launch_bounds__(SEL_T) void topk_select_kernel(const uint16_t* __re
     int tot;
     int og = block_excl_scan(cg, sh, tot);
     int oe = block_excl_scan(ce, sh, tot);
-    for (int i = lo; i < hi; ++i) {
-        const int key = kq[i];
-        if (key > T) { cand[og++] = ((unsigned long long)key << 32) | (unsigned)(0x7fffffff - i); }
-        else if (key == T) { if (oe < need_eq) cand[ngt + oe] = ((unsigned long long)key << 32) | (unsigned)(0x7fffffff - i); ++oe; }
-    }
+    for (int i = lo; i < hi; ++i) cand_place(cand, kq[i], i, T, ngt, need_eq, og, oe);
     // pad to a power of two and bitonic-sort descending on (key, -index)
-    int n2 = 1;
-    while (n2 < k) n2 <<= 1;
-    for (int i = k + tid; i < n2; i += SEL_T) cand[i] = 0ull;
-    __syncthreads();
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < n2; i += SEL_T) {
-                const int j = i ^ stride;
-                if (j > i) {
-                    const bool desc = ((i & size) == 0);
-                    const unsigned long long a = cand[i], b = cand[j];
-                    if ((a < b) == desc) { cand[i] = b; cand[j] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    for (int i = tid; i < k; i += SEL_T) {
-        const unsigned long long c = cand[i];
-        out_scores[(size_t)q * k + i] = key16_to_float((uint32_t)(c >> 32));
-        out_idx[(size_t)q * k + i] = idx_offset + (0x7fffffff - (int)(unsigned)(c & 0xffffffffu));
-    }
+    cand_sort_emit(cand, q, k, tid, idx_offset, out_scores, out_idx);
 }
 
 // ---- register-resident select (N <= 48 * SEL_T keys per query) ---------------------------------------------------------------
@@ -244,24 +265,6 @@ __global__ __launch_bounds__(SEL_T) void topk_select_kernel(const uint16_t* __re
 //      survivors, as before.  Same total order (key desc, index asc) -> bit-identical results.
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-    v += __float_as_int(lane_xor<32>(__int_as_float(v)));
-    v += __float_as_int(lane_xor<16>(__int_as_float(v)));
-    v += __float_as_int(lane_xor<8>(__int_as_float(v)));
-    v += __float_as_int(lane_xor<4>(__int_as_float(v)));
-    v += __float_as_int(lane_xor<2>(__int_as_float(v)));
-    v += __float_as_int(lane_xor<1>(__int_as_float(v)));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-    v = max(v, __float_as_int(lane_xor<32>(__int_as_float(v))));
-    v = max(v, __float_as_int(lane_xor<16>(__int_as_float(v))));
-    v = max(v, __float_as_int(lane_xor<8>(__int_as_float(v))));
-    v = max(v, __float_as_int(lane_xor<4>(__int_as_float(v))));
-    v = max(v, __float_as_int(lane_xor<2>(__int_as_float(v))));
-    v = max(v, __float_as_int(lane_xor<1>(__int_as_float(v))));
-    return v;
-}
 constexpr int SEL_W = 24;                 // packed words per thread: thread t owns keys [48 t, 48 t + 48)
 constexpr int SEL_CAP = SEL_T * 2 * SEL_W;   // 49 152 keys
 
@@ -354,18 +357,10 @@ __global__ __launch_bounds__(SEL_T) void topk_select_reg_kernel(const uint16_t* 
                 const int b = __ffsll((long long)gem) - 1;
                 gem &= gem - 1;
                 const int i = lo + b;
-                cand[off++] = ((unsigned long long)lkeys[i] << 32) | (unsigned)(0x7fffffff - i);
+                cand[off++] = cand_pack(lkeys[i], i);
             }
             __syncthreads();
-            if (tid < M) {
-                const unsigned long long mine = cand[tid];
-                int rank = 0;
-                for (int j = 0; j < M; ++j) rank += cand[j] > mine;
-                if (rank < k) {
-                    out_scores[(size_t)q * k + rank] = key16_to_float((uint32_t)(mine >> 32));
-                    out_idx[(size_t)q * k + rank] = idx_offset + (0x7fffffff - (int)(unsigned)(mine & 0xffffffffu));
-                }
-            }
+            rank_sort_emit(cand, M, q, k, tid, idx_offset, out_scores, out_idx);
             return;
         }
     }
@@ -409,44 +404,12 @@ __global__ __launch_bounds__(SEL_T) void topk_select_reg_kernel(const uint16_t* 
         for (int h = 0; h < 2; ++h) {
             const int i = lo + 2 * j + h;
             if (i >= hi) continue;
-            const int key = h ? (int)(w[j] >> 16) : (int)(w[j] & 0xffffu);
-            if (key > T) cand[og++] = ((unsigned long long)key << 32) | (unsigned)(0x7fffffff - i);
-            else if (key == T) { if (oe < need_eq) cand[ngt + oe] = ((unsigned long long)key << 32) | (unsigned)(0x7fffffff - i); ++oe; }
+            cand_place(cand, h ? (int)(w[j] >> 16) : (int)(w[j] & 0xffffu), i, T, ngt, need_eq, og, oe);
         }
     }
     __syncthreads();
-    if (k <= 256) {
-        // rank sort: candidates are distinct 64-bit values; a candidate's rank is the number of larger ones (broadcast LDS reads)
-        if (tid < k) {
-            const unsigned long long mine = cand[tid];
-            int rank = 0;
-            for (int j = 0; j < k; ++j) rank += cand[j] > mine;
-            out_scores[(size_t)q * k + rank] = key16_to_float((uint32_t)(mine >> 32));
-            out_idx[(size_t)q * k + rank] = idx_offset + (0x7fffffff - (int)(unsigned)(mine & 0xffffffffu));
-        }
-        return;
-    }
-    int n2 = 1;
-    while (n2 < k) n2 <<= 1;
-    for (int i = k + tid; i < n2; i += SEL_T) cand[i] = 0ull;
-    __syncthreads();
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < n2; i += SEL_T) {
-                const int j = i ^ stride;
-                if (j > i) {
-                    const bool desc = ((i & size) == 0);
-                    const unsigned long long a = cand[i], b = cand[j];
-                    if ((a < b) == desc) { cand[i] = b; cand[j] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    for (int i = tid; i < k; i += SEL_T) {
-        const unsigned long long c = cand[i];
-        out_scores[(size_t)q * k + i] = key16_to_float((uint32_t)(c >> 32));
-        out_idx[(size_t)q * k + i] = idx_offset + (0x7fffffff - (int)(unsigned)(c & 0xffffffffu));
-    }
+    if (k <= 256) rank_sort_emit(cand, k, q, k, tid, idx_offset, out_scores, out_idx);   // the k candidates ARE the answer: order them
+    else cand_sort_emit(cand, q, k, tid, idx_offset, out_scores, out_idx);
 }
 
 // merge C candidates (score f32 holding a bf16 value, global idx) per query down to k, same ordering
@@ -464,29 +427,18 @@ __global__ __launch_bounds__(1024) void topk_merge_kernel(const float* __restric
             // full 32-bit sortable key (scores are bf16 values, but keep it generic)
             uint32_t b = __float_as_uint(s);
             b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-            v = ((unsigned long long)b << 32) | (unsigned)(0x7fffffff - ci[(size_t)q * C + i]);
+            v = cand_pack(b, ci[(size_t)q * C + i]);
         }
         mc[i] = v;
     }
     __syncthreads();
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < n2; i += blockDim.x) {
-                const int j = i ^ stride;
-                if (j > i) {
-                    const bool desc = ((i & size) == 0);
-                    const unsigned long long a = mc[i], b = mc[j];
-                    if ((a < b) == desc) { mc[i] = b; mc[j] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    lds_bitonic_desc(mc, n2, tid, blockDim.x);
     for (int i = tid; i < k; i += blockDim.x) {
         const unsigned long long c = mc[i];
         uint32_t b = (uint32_t)(c >> 32);
         b = (b & 0x80000000u) ? (b & 0x7fffffffu) : ~b;
         out_scores[(size_t)q * k + i] = __uint_as_float(b);
-        out_idx[(size_t)q * k + i] = 0x7fffffff - (int)(unsigned)(c & 0xffffffffu);
+        out_idx[(size_t)q * k + i] = cand_index(c);
     }
 }
 
@@ -496,19 +448,7 @@ __global__ __launch_bounds__(1024) void topk_merge_kernel(const float* __restric
 //   tn = bf16(t / max(bf16(||t||), eps)) per patch row;  d[t,p] = bf16( tn . qn[p] );
 //   score[t] = bf16( (sum_p d[t,p]) / P )
 // qn is the already-normalised (or, frame-0 quirk, raw) query [P, D]; weights optional [T,P] f32
-// (mask_scores variant: score = sum(d*w)/sum(w)).
-// bf16( x / n ) with the IEEE quotient's rounding but without its ~12-instruction expansion: r = v_rcp_f32(n) (1 ulp), one
-// residual correction step puts q within 1 fp32 ulp of the correctly rounded quotient, and that can only change the
-// bf16 rounding when q's discarded 16 bits sit next to the midpoint 0x8000 — only those lanes (9 in 65536) take the exact
-// division.  Bit-identical to rbf(__fdiv_rn(x, n)) (what the oracle computes); the kernel was VALU-bound on the divisions.
-__device__ __forceinline__ float div_rbf(float x, float n, float r) {
-    float q = x * r;
-    const float e = __fmaf_rn(-q, n, x);
-    q = __fmaf_rn(e, r, q);
-    if ((__float_as_uint(q) & 0xffffu) - 0x7ffcu <= 8u) q = __fdiv_rn(x, n);
-    return rbf(q);
-}
-
+// (mask_scores variant: score = sum(d*w)/sum(w)).  The normalise-then-dot of one row is dot64.h's d64_normed_dot (div_rbf).
 template <int NCH>
 __global__ __launch_bounds__(256) void template_dots_kernel(const bf16_t* __restrict__ tmpl,
                                                             const bf16_t* __restrict__ qn, float* __restrict__ dots,
@@ -519,49 +459,18 @@ __global__ __launch_bounds__(256) void template_dots_kernel(const bf16_t* __rest
     const long rows = (long)T * P;
     // the row a wave will process NEXT is requested before the current one is reduced: two rows (4 KB) in flight per wave
     uint4 na[NCH], nb[NCH];
-    auto fetch = [&](long r) {
-        const int pidx = (int)(r % P);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int base = (c * 64 + lane) * 8;
-            na[c] = make_uint4(0, 0, 0, 0);
-            nb[c] = make_uint4(0, 0, 0, 0);
-            if (base < D) {
-                na[c] = *(const uint4*)(tmpl + (size_t)r * D + base);
-                nb[c] = *(const uint4*)(qn + (size_t)pidx * D + base);
-            }
-        }
-    };
+    auto fetch = [&](long r) { d64_load2<NCH>(na, tmpl + (size_t)r * D, nb, qn + (size_t)(r % P) * D, D, lane); };
     if (wave < rows) fetch(wave);
     for (long r = wave; r < rows; r += nwave) {
         float x[NCH][8], qq[NCH][8];
-        float ss = 0.f;
         uint4 ca[NCH], cb[NCH];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) { ca[c] = na[c]; cb[c] = nb[c]; }
         if (r + nwave < rows) fetch(r + nwave);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const uint4 a = ca[c], b = cb[c];
-            const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                x[c][2 * e] = lo_bf(aw[e]); x[c][2 * e + 1] = hi_bf(aw[e]);
-                qq[c][2 * e] = lo_bf(bw[e]); qq[c][2 * e + 1] = hi_bf(bw[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss = __fmaf_rn(x[c][e], x[c][e], ss);
-        }
-        ss = wave_sum(ss);
-        const float nrm = fmaxf(rbf(fp_sqrt_rn(ss)), 1e-12f);
-        const float rinv = __builtin_amdgcn_rcpf(nrm);
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc = __fmaf_rn(div_rbf(x[c][e], nrm, rinv), qq[c][e], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) dots[r] = rbf(acc);
+        d64_unpack(ca, x);
+        d64_unpack(cb, qq);
+        const float d = d64_normed_dot<NCH>(x, qq);
+        if (lane == 0) dots[r] = d;
     }
 }
 
@@ -579,40 +488,18 @@ __global__ __launch_bounds__(256) void template_dots_normed_kernel(const bf16_t*
     const int pidx = wave / TS, t0 = wave % TS;
     if (pidx >= P) return;
     float qq[NCH][8];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int base = (c * 64 + lane) * 8;
-        uint4 b = make_uint4(0, 0, 0, 0);
-        if (base < D) b = *(const uint4*)(qn + (size_t)pidx * D + base);
-        const uint32_t bw[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { qq[c][2 * e] = lo_bf(bw[e]); qq[c][2 * e + 1] = hi_bf(bw[e]); }
+    {
+        uint4 b[NCH];
+        d64_load<NCH>(b, qn, (size_t)pidx * D, D, lane);
+        d64_unpack(b, qq);
     }
     const size_t tstride = (size_t)P * D;
     const bf16_t* row = tn + (size_t)pidx * D;
-    auto fetch = [&](int t, uint4 (&dst)[NCH]) {
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int base = (c * 64 + lane) * 8;
-            dst[c] = make_uint4(0, 0, 0, 0);
-            if (base < D && t < T) {
-                typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
-                const u32x4_t v = __builtin_nontemporal_load((const u32x4_t*)(row + (size_t)t * tstride + base));
-                dst[c] = make_uint4(v.x, v.y, v.z, v.w);
-            }
-        }
-    };
+    auto fetch = [&](int t, uint4 (&dst)[NCH]) { d64_load<NCH, false, true>(dst, row, (size_t)t * tstride, D, lane, t < T); };
     auto reduce = [&](const uint4 (&src)[NCH], int t) {
         float acc = 0.f;
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const uint32_t aw[4] = {src[c].x, src[c].y, src[c].z, src[c].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc = __fmaf_rn(lo_bf(aw[e]), qq[c][2 * e], acc);
-                acc = __fmaf_rn(hi_bf(aw[e]), qq[c][2 * e + 1], acc);
-            }
-        }
+        for (int c = 0; c < NCH; ++c) acc = d64_dot(src[c], qq[c], acc);
         acc = wave_sum(acc);
         if (lane == 0) dots[(size_t)t * P + pidx] = rbf(acc);
     };
@@ -674,55 +561,21 @@ __global__ __launch_bounds__(256) void rerank_views_kernel(const bf16_t* __restr
     const int r0 = offsets[mesh], nv = min(offsets[mesh + 1] - r0, RR_MAXV);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float qv[NCH][8];
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-        const int base = (ch * 64 + lane) * 8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qv[ch][e] = base < D ? bf2f(queries[(size_t)q * D + base + e]) : 0.f;
-    }
+    d64_load_elems<NCH>(qv, queries + (size_t)q * D, D, lane);   // element-wise: the caller's query rows need not be 16-byte aligned
     for (int v = wave; v < nv; v += 4) {
-        const bf16_t* row = views + (size_t)(r0 + v) * D;
+        uint4 a[NCH];
         float x[NCH][8];
-        float ss = 0.f;
-#pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) {
-            const int base = (ch * 64 + lane) * 8;
-            uint4 a = make_uint4(0, 0, 0, 0);
-            if (base < D) a = *(const uint4*)(row + base);
-            const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { x[ch][2 * e] = lo_bf(w[e]); x[ch][2 * e + 1] = hi_bf(w[e]); }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss = __fmaf_rn(x[ch][e], x[ch][e], ss);
-        }
-        ss = wave_sum(ss);
-        const float nrm = fmaxf(rbf(fp_sqrt_rn(ss)), 1e-12f);
-        const float rinv = __builtin_amdgcn_rcpf(nrm);
-        float acc = 0.f;
-#pragma unroll
-        for (int ch = 0; ch < NCH; ++ch)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc = __fmaf_rn(div_rbf(x[ch][e], nrm, rinv), qv[ch][e], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) sc[v] = rbf(acc);
+        d64_load<NCH>(a, views, (size_t)(r0 + v) * D, D, lane);
+        d64_unpack(a, x);
+        const float s = d64_normed_dot<NCH>(x, qv);
+        if (lane == 0) sc[v] = s;
     }
     int n2 = 1;
     while (n2 < nv) n2 <<= 1;
     __syncthreads();
     for (int i = nv + threadIdx.x; i < n2; i += blockDim.x) sc[i] = -3.0e38f;
     __syncthreads();
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += blockDim.x) {
-                const int j = i ^ stride;
-                if (j > i) {
-                    const bool desc = ((i & size) == 0);
-                    const float a = sc[i], b = sc[j];
-                    if ((a < b) == desc) { sc[i] = b; sc[j] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    lds_bitonic_desc(sc, n2, threadIdx.x, blockDim.x);
     if (threadIdx.x == 0) {
         // numpy float32 mean of the kk top values: pairwise summation (8 running sums, tree, sequential tail; n <= 128)
         const int kk = min(k, nv);
@@ -780,17 +633,16 @@ int fp_bank_scan(const bf16_t* bank, const bf16_t* queries, uint16_t* keys, int 
             hipLaunchKernelGGL((bank_scan_kernel<NCHV, QTV, false>), dim3(blocks), dim3(256), 0, s, bank, queries,  \
                                keys, N, D, qb, Q, ldk);                                                             \
     } while (0)
+        const int qt = left >= 4 ? 4 : 1;
         // (8 queries per pass was measured in round 4 — profiles/r04_ab.md §3: 44.4 us against 2 x 21.9 us for two 4-query passes.
         // Beyond one query the pass is bound by vector-ALU issue, ~4 us per extra query, and at 8 x 16 unpacked query values per
         // lane the kernel drops to one wave per SIMD; a matrix-pipe form would change the canonical summation order that makes the
         // indices bit-exact.  Four per pass stays.)
-        if (left >= 4) {
-            if (nch == 1) FP_SCAN(1, 4); else if (nch == 2) FP_SCAN(2, 4); else FP_SCAN(3, 4);
-            qb += 4;
-        } else {
-            if (nch == 1) FP_SCAN(1, 1); else if (nch == 2) FP_SCAN(2, 1); else FP_SCAN(3, 1);
-            qb += 1;
-        }
+        fp_nch_dispatch(nch, [&](auto c) {
+            constexpr int NCH = decltype(c)::value;
+            if (qt == 4) FP_SCAN(NCH, 4); else FP_SCAN(NCH, 1);
+        });
+        qb += qt;
 #undef FP_SCAN
         FP_LAUNCH_CHECK();
     }
@@ -841,24 +693,17 @@ int fp_template_score_launch(const bf16_t* tmpl, const bf16_t* qn, const float* 
                       int P, int D, int templates_normalised, hipStream_t s) {
     FP_REQUIRE(T > 0 && P > 0 && D % 8 == 0 && D <= 1536, "template_score: bad shape");
     const long rows = (long)T * P;
-    if (templates_normalised) {
-        // ~16 waves per CU in flight: TS template slices per patch index
-        const int TS = std::max(1, std::min(T, cdiv(256 * 16, P)));
-        const int nblk = cdiv(P * TS, 4);
-        const int nchn = cdiv(D, 512);
-        if (nchn == 1) hipLaunchKernelGGL(template_dots_normed_kernel<1>, dim3(nblk), dim3(256), 0, s, tmpl, qn, dots, T, P, D, TS);
-        else if (nchn == 2) hipLaunchKernelGGL(template_dots_normed_kernel<2>, dim3(nblk), dim3(256), 0, s, tmpl, qn, dots, T, P, D, TS);
-        else hipLaunchKernelGGL(template_dots_normed_kernel<3>, dim3(nblk), dim3(256), 0, s, tmpl, qn, dots, T, P, D, TS);
-        FP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(template_mean_kernel, dim3(T), dim3(64), 0, s, dots, weights, scores, T, P);
-        FP_LAUNCH_CHECK();
-        return FP_OK;
-    }
-    const int blocks = (int)std::min<long>((rows + 3) / 4, 256 * 16);
-    const int nch = cdiv(D, 512);
-    if (nch == 1) hipLaunchKernelGGL(template_dots_kernel<1>, dim3(blocks), dim3(256), 0, s, tmpl, qn, dots, T, P, D);
-    else if (nch == 2) hipLaunchKernelGGL(template_dots_kernel<2>, dim3(blocks), dim3(256), 0, s, tmpl, qn, dots, T, P, D);
-    else hipLaunchKernelGGL(template_dots_kernel<3>, dim3(blocks), dim3(256), 0, s, tmpl, qn, dots, T, P, D);
+    fp_nch_dispatch(cdiv(D, 512), [&](auto c) {
+        constexpr int NCH = decltype(c)::value;
+        if (templates_normalised) {
+            // ~16 waves per CU in flight: TS template slices per patch index
+            const int TS = std::max(1, std::min(T, cdiv(256 * 16, P)));
+            hipLaunchKernelGGL(template_dots_normed_kernel<NCH>, dim3(cdiv(P * TS, 4)), dim3(256), 0, s, tmpl, qn, dots, T, P, D, TS);
+        } else {
+            const int blocks = (int)std::min<long>((rows + 3) / 4, 256 * 16);
+            hipLaunchKernelGGL(template_dots_kernel<NCH>, dim3(blocks), dim3(256), 0, s, tmpl, qn, dots, T, P, D);
+        }
+    });
     FP_LAUNCH_CHECK();
     hipLaunchKernelGGL(template_mean_kernel, dim3(T), dim3(64), 0, s, dots, weights, scores, T, P);
     FP_LAUNCH_CHECK();
@@ -869,11 +714,9 @@ int fp_template_score_launch(const bf16_t* tmpl, const bf16_t* qn, const float* 
 int fp_rerank_views_launch(const bf16_t* views, const int* offsets, const int* cand, const bf16_t* queries, float* out,
                            int Q, int C, int D, int k, hipStream_t s) {
     FP_REQUIRE(Q > 0 && C > 0 && D % 8 == 0 && D <= 1536 && k > 0 && k <= 128, "rerank_views: bad shape");
-    const int nch = cdiv(D, 512);
-    dim3 grid(C, Q);
-    if (nch == 1) hipLaunchKernelGGL(rerank_views_kernel<1>, grid, dim3(256), 0, s, views, offsets, cand, queries, out, C, D, k);
-    else if (nch == 2) hipLaunchKernelGGL(rerank_views_kernel<2>, grid, dim3(256), 0, s, views, offsets, cand, queries, out, C, D, k);
-    else hipLaunchKernelGGL(rerank_views_kernel<3>, grid, dim3(256), 0, s, views, offsets, cand, queries, out, C, D, k);
+    fp_nch_dispatch(cdiv(D, 512), [&](auto c) {
+        hipLaunchKernelGGL(rerank_views_kernel<decltype(c)::value>, dim3(C, Q), dim3(256), 0, s, views, offsets, cand, queries, out, C, D, k);
+    });
     FP_LAUNCH_CHECK();
     return FP_OK;
 }

@@ -8,6 +8,7 @@
 //   ffa           : mask any-pool 14x14 -> masked mean over patches -> optional L2 normalise
 //                   (scripts/extract_retrieval_features.py:51-57, extract_proposals_ground.py:129-134)
 #include "internal.h"
+#include "dot64.h"
 #include "gemm_bf16.h"
 
 namespace {
@@ -88,23 +89,17 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
     for (int r = wave; r < rows; r += nwave) {
         const size_t ir = (size_t)(r / rows_per_b) * in_stride_b + in_off + (r % rows_per_b);
         const bf16_t* xr = X + ir * D;
+        uint4 xw[MAXC];
         float v[MAXC][8];
+        d64_load<MAXC>(xw, xr, 0, D, lane);
+        d64_unpack(xw, v);
         float sum = 0.f;
 #pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ch = lane + 64 * c;
-            if (ch < nch) {
-                const uint4 q = *(const uint4*)(xr + ch * 8);
-                const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[c][2 * e] = lo_bf(w[e]); v[c][2 * e + 1] = hi_bf(w[e]); }
+        for (int c = 0; c < MAXC; ++c)
+            if (lane + 64 * c < nch) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) sum += v[c][e];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[c][e] = 0.f;
             }
-        }
         const float mean = wave_sum(sum) / (float)D;
         float sq = 0.f;
 #pragma unroll
@@ -115,7 +110,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
             }
         const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
         bf16_t* yr = Y + (size_t)r * D;
-        uint32_t keep[MAXC][4];
+        uint4 keep[MAXC];
         float acc = 0.f;
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
@@ -131,32 +126,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
                     o[e] = pack_bf2(a, b);
                 }
                 if (L2) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        keep[c][e] = o[e];
-                        const float lo = lo_bf(o[e]), hi = hi_bf(o[e]);
-                        acc = __fmaf_rn(lo, lo, acc);
-                        acc = __fmaf_rn(hi, hi, acc);
-                    }
+                    keep[c] = make_uint4(o[0], o[1], o[2], o[3]);
+                    acc = d64_sumsq(keep[c], acc);
                 } else {
                     *(uint4*)(yr + ch * 8) = make_uint4(o[0], o[1], o[2], o[3]);
                 }
             }
         }
-        if (L2) {
-            acc = wave_sum(acc);
-            const float n = fmaxf(rbf(fp_sqrt_rn(acc)), 1e-12f);
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                const int ch = lane + 64 * c;
-                if (ch < nch) {
-                    uint32_t o[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(__fdiv_rn(lo_bf(keep[c][e]), n), __fdiv_rn(hi_bf(keep[c][e]), n));
-                    *(uint4*)(yr + ch * 8) = make_uint4(o[0], o[1], o[2], o[3]);
-                }
-            }
-        }
+        if (L2) d64_norm_store<MAXC>(keep, d64_row_norm(wave_sum(acc)), yr, D, lane);
     }
 }
 
@@ -313,46 +290,33 @@ __global__ __launch_bounds__(1024) void ffa_kernel(const bf16_t* __restrict__ fe
     }
     __syncthreads();
     if (!last_s || threadIdx.x >= 64) return;
-    // one wave: l2norm_rows_kernel's arithmetic (lane l takes elements (c*64 + l)*8 + e, fmaf chain, xor-butterfly), 16-byte accesses
+    // one wave: l2norm_rows_kernel's arithmetic (dot64.h), 16-byte accesses; any D, so the row is read twice instead of held
     const int lane = threadIdx.x;
     const bf16_t* xr = out + (size_t)b * D;
     float acc = 0.f;
-    for (int base = lane * 8; base < D; base += 512) {
-        const uint4 q = *(const uint4*)(xr + base);
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float lo = lo_bf(w[e]), hi = hi_bf(w[e]); acc = __fmaf_rn(lo, lo, acc); acc = __fmaf_rn(hi, hi, acc); }
-    }
-    acc = wave_sum(acc);
-    const float n = fmaxf(rbf(fp_sqrt_rn(acc)), 1e-12f);
-    for (int base = lane * 8; base < D; base += 512) {
-        const uint4 q = *(const uint4*)(xr + base);
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-        uint32_t o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = pack_bf2(__fdiv_rn(lo_bf(w[e]), n), __fdiv_rn(hi_bf(w[e]), n));
-        *(uint4*)(out_norm + (size_t)b * D + base) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
+    for (int base = lane * 8; base < D; base += 512) acc = d64_sumsq(*(const uint4*)(xr + base), acc);
+    const float n = d64_row_norm(wave_sum(acc));
+    for (int base = lane * 8; base < D; base += 512) d64_norm_store(*(const uint4*)(xr + base), n, out_norm + (size_t)b * D + base);
 }
 
-// F.normalize(x, dim=-1) on bf16 rows with the reference's rounding points:
-//   n = bf16(sqrt(sum x^2)) ; y = bf16(x / max(n, eps))
-// sum order: lane l takes elements (c*64 + l)*8 + e, fmaf chain, then xor-butterfly (canonical, see oracle)
+// F.normalize(x, dim=-1) on bf16 rows with the reference's rounding points and the canonical sum order (dot64.h), for any D and any
+// alignment: element-wise accesses, the row read twice
 __global__ __launch_bounds__(64) void l2norm_rows_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y,
                                                          int rows, int D) {
     const int r = blockIdx.x, lane = threadIdx.x;
     if (r >= rows) return;
     const bf16_t* xr = X + (size_t)r * D;
+    float x[8];
     float acc = 0.f;
     for (int base = lane * 8; base < D; base += 512) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float v = bf2f(xr[base + e]); acc = __fmaf_rn(v, v, acc); }
+        d64_load_elems(x, xr, base, D);
+        acc = d64_sumsq(x, acc);
     }
-    acc = wave_sum(acc);
-    const float n = fmaxf(rbf(fp_sqrt_rn(acc)), 1e-12f);
+    const float n = d64_row_norm(wave_sum(acc));
     for (int base = lane * 8; base < D; base += 512) {
+        d64_load_elems(x, xr, base, D);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) Y[(size_t)r * D + base + e] = f2bf(__fdiv_rn(bf2f(xr[base + e]), n));
+        for (int e = 0; e < 8; ++e) Y[(size_t)r * D + base + e] = d64_div_bf(x[e], n);
     }
 }
 
@@ -364,35 +328,11 @@ __global__ __launch_bounds__(256) void l2norm_rows_vec_kernel(const bf16_t* X, b
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     uint4 a[NCH];
+    d64_load<NCH>(a, X, (size_t)r * D, D, lane);
     float acc = 0.f;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int base = (c * 64 + lane) * 8;
-        a[c] = make_uint4(0, 0, 0, 0);
-        if (base < D) a[c] = *(const uint4*)(X + (size_t)r * D + base);
-        const uint32_t w[4] = {a[c].x, a[c].y, a[c].z, a[c].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float lo = __uint_as_float(w[e] << 16), hi = __uint_as_float(w[e] & 0xffff0000u);
-            acc = __fmaf_rn(lo, lo, acc);
-            acc = __fmaf_rn(hi, hi, acc);
-        }
-    }
-    acc = wave_sum(acc);
-    const float n = fmaxf(rbf(fp_sqrt_rn(acc)), 1e-12f);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int base = (c * 64 + lane) * 8;
-        if (base >= D) continue;
-        const uint32_t w[4] = {a[c].x, a[c].y, a[c].z, a[c].w};
-        uint32_t o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float lo = __fdiv_rn(__uint_as_float(w[e] << 16), n), hi = __fdiv_rn(__uint_as_float(w[e] & 0xffff0000u), n);
-            o[e] = (__float_as_uint(rbf(lo)) >> 16) | (__float_as_uint(rbf(hi)) & 0xffff0000u);
-        }
-        *(uint4*)(Y + (size_t)r * D + base) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
+    for (int c = 0; c < NCH; ++c) acc = d64_sumsq(a[c], acc);
+    d64_norm_store<NCH>(a, d64_row_norm(wave_sum(acc)), Y + (size_t)r * D, D, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -588,9 +528,9 @@ int fp_l2norm_rows(const bf16_t* X, bf16_t* Y, int rows, int D, hipStream_t s) {
     const int nch = cdiv(D, 512);
     const bool aligned = (((uintptr_t)X | (uintptr_t)Y) & 15) == 0;
     if (nch <= 3 && aligned) {   // in-place (X == Y) is fine: a wave reads its whole row before it writes
-        if (nch == 1) hipLaunchKernelGGL(l2norm_rows_vec_kernel<1>, dim3(cdiv(rows, 4)), dim3(256), 0, s, X, Y, rows, D);
-        else if (nch == 2) hipLaunchKernelGGL(l2norm_rows_vec_kernel<2>, dim3(cdiv(rows, 4)), dim3(256), 0, s, X, Y, rows, D);
-        else hipLaunchKernelGGL(l2norm_rows_vec_kernel<3>, dim3(cdiv(rows, 4)), dim3(256), 0, s, X, Y, rows, D);
+        fp_nch_dispatch(nch, [&](auto c) {
+            hipLaunchKernelGGL(l2norm_rows_vec_kernel<decltype(c)::value>, dim3(cdiv(rows, 4)), dim3(256), 0, s, X, Y, rows, D);
+        });
     } else
     hipLaunchKernelGGL(l2norm_rows_kernel, dim3(rows), dim3(64), 0, s, X, Y, rows, D);
     FP_LAUNCH_CHECK();

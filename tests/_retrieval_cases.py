@@ -12,13 +12,13 @@ import functools
 import numpy as np
 
 # ---- constants of freepose_amd/csrc/retrieval.hip (line numbers as of this file's writing) ------------------------------------------------------------------------------------------------
-RU = 4                            # retrieval.hip:44   rows per chunk of bank_scan_kernel
-SEL_T = 1024                      # retrieval.hip:122  threads of a select workgroup
-KMAX = 1024                       # retrieval.hip:123  largest k, and the capacity of the candidate buffer
-SEL_W = 24                        # retrieval.hip:265  packed words per thread: a thread owns 2 * SEL_W = 48 consecutive keys
-SEL_CAP = SEL_T * 2 * SEL_W       # retrieval.hip:266  49 152 keys: the register kernel's largest row
-RR_MAXV = 1024                    # retrieval.hip:666  views per mesh the re-rank looks at
-HIST_LDS_MAX = 65536              # retrieval.hip:818  key_bytes <= 128 KB  <=>  padded row <= 65 536 keys
+RU = 4                            # retrieval.hip:38   rows per chunk of bank_scan_kernel
+SEL_T = 1024                      # retrieval.hip:111  threads of a select workgroup
+KMAX = 1024                       # retrieval.hip:112  largest k, and the capacity of the candidate buffer
+SEL_W = 24                        # retrieval.hip:268  packed words per thread: a thread owns 2 * SEL_W = 48 consecutive keys
+SEL_CAP = SEL_T * 2 * SEL_W       # retrieval.hip:269  49 152 keys: the register kernel's largest row
+RR_MAXV = 1024                    # retrieval.hip:553  views per mesh the re-rank looks at
+HIST_LDS_MAX = 65536              # retrieval.hip:670  key_bytes <= 128 KB  <=>  padded row <= 65 536 keys
 PER = 2 * SEL_W
 
 Q_E0, Q_NEG, Q_TWO = 0x3F80, 0xBF80, 0x4000     # bf16 bits of the three planted queries' first element: 1, -1, 2
@@ -86,7 +86,7 @@ def merge_ref(cs, ci, k: int):
 
 # ---- mirror of the dispatch predicates ----------------------------------------------------------------------------------------------
 def scan_rows_per_wave(N: int, ncu: int):
-    """fp_bank_scan's grid choice (retrieval.hip:762-771): (base_rows, rem, nwave); the first `rem` waves own base_rows + 1 rows"""
+    """fp_bank_scan's grid choice (retrieval.hip:615-624): (base_rows, rem, nwave); the first `rem` waves own base_rows + 1 rows"""
     blocks, best = ncu * 2, 1e30
     for bpc in range(2, 9):
         nw = ncu * bpc * 4
@@ -99,7 +99,7 @@ def scan_rows_per_wave(N: int, ncu: int):
 
 
 def scan_inloop_fetches(rows: int) -> int:
-    """how often a wave that owns `rows` rows executes the in-loop fetch(bufB, r0 + RU) (retrieval.hip:110)"""
+    """how often a wave that owns `rows` rows executes the in-loop fetch(bufB, r0 + RU) (retrieval.hip:99)"""
     return sum(1 for r0 in range(2 * RU, rows, 2 * RU) if r0 + RU < rows)
 
 
@@ -124,13 +124,13 @@ def scan_n_for(base_rows: int, ncu: int) -> int:
 
 
 def scan_form(D: int):
-    """(NCH, FULL) of the bank_scan_kernel instantiation fp_bank_scan launches for D (retrieval.hip:759, 776)"""
+    """(NCH, FULL) of the bank_scan_kernel instantiation fp_bank_scan launches for D (retrieval.hip:612, 629)"""
     nch = (D + 511) // 512
     return nch, D == nch * 512
 
 
 def scan_passes(Q: int):
-    """queries per pass (retrieval.hip:787-793): 4 while at least 4 are left, then one at a time"""
+    """queries per pass (retrieval.hip:636-645): 4 while at least 4 are left, then one at a time"""
     out = []
     while Q >= 4:
         out.append(4)
@@ -145,41 +145,41 @@ def select_path(keys, k: int) -> dict:
     N = len(keys)
     assert 0 < k <= KMAX and k <= N
     ldk = (N + 7) & ~7
-    if N > SEL_CAP:                                    # retrieval.hip:811
+    if N > SEL_CAP:                                    # retrieval.hip:663
         hist = np.bincount(keys >> 8, minlength=256)
         c, b = 0, 255
-        while b >= 0 and c + hist[b] < k:              # retrieval.hip:181
+        while b >= 0 and c + hist[b] < k:              # retrieval.hip:226
             c += hist[b]
             b -= 1
         hi_exact = c + hist[b] == k
         hb = b
         hist = np.bincount(keys[(keys >> 8) == hb] & 255, minlength=256)
         b = 255
-        while b >= 0 and c + hist[b] < k:              # retrieval.hip:194
+        while b >= 0 and c + hist[b] < k:              # retrieval.hip:239
             c += hist[b]
             b -= 1
         lo_exact = c + hist[b] == k
         T = (hb << 8) | b
         return dict(path="hist-lds" if ldk <= HIST_LDS_MAX else "hist-global", T=T, ngt=int(c), neq=int((keys == T).sum()),
                     hi_exact=bool(hi_exact), lo_exact=bool(lo_exact), hi_bins=int((np.bincount(keys >> 8, minlength=256) > 0).sum()))
-    row = np.zeros(SEL_CAP, dtype=np.int64)            # staged row: zero beyond N (retrieval.hip:289)
+    row = np.zeros(SEL_CAP, dtype=np.int64)            # staged row: zero beyond N (retrieval.hip:292)
     row[:N] = keys
-    maxima = row.reshape(SEL_T, PER).max(axis=1)       # retrieval.hip:309-312
+    maxima = row.reshape(SEL_T, PER).max(axis=1)       # retrieval.hip:312-315
     G = int(maxima.max())
     L = 0
-    for bit in range(15, -1, -1):                      # retrieval.hip:333-337
+    for bit in range(15, -1, -1):                      # retrieval.hip:336-340
         c = L | (1 << bit)
         if c > G:
             continue
         if int((maxima >= c).sum()) >= k:
             L = c
-    M = int((row >= max(L, 1)).sum())                  # retrieval.hip:343-351
+    M = int((row >= max(L, 1)).sum())                  # retrieval.hip:346-354
     out = dict(L=L, G=G, M=M, T=None, ngt=None, iters=0)
     if M <= KMAX:
         out.update(path="reg-fast")
         return out
     tlo, thi, it = L, G, 0
-    while tlo < thi:                                   # retrieval.hip:386-389
+    while tlo < thi:                                   # retrieval.hip:381-384
         mid = (tlo + thi + 1) >> 1
         if int((row >= mid).sum()) >= k:
             tlo = mid
@@ -198,7 +198,7 @@ def select_path(keys, k: int) -> dict:
 
 
 def normed_ts(T: int, P: int):
-    """fp_template_score_launch, normalised store (retrieval.hip:846): (TS, sorted set of how many templates a wave owns, number of waves
+    """fp_template_score_launch, normalised store (retrieval.hip:700): (TS, sorted set of how many templates a wave owns, number of waves
     launched with pidx >= P)"""
     TS = max(1, min(T, (256 * 16 + P - 1) // P))
     owns = sorted({len(range(t0, T, TS)) for t0 in range(TS)})
@@ -439,7 +439,7 @@ def div_observed(bits) -> np.ndarray:
 
 
 def div_fallback_lanes(q) -> np.ndarray:
-    """quotients whose low 16 bits lie within 4 of 0x8000: where div_rbf must take the exact division (retrieval.hip:508)"""
+    """quotients whose low 16 bits lie within 4 of 0x8000: where div_rbf must take the exact division (dot64.h:136)"""
     low = (np.ascontiguousarray(q, np.float32).view(np.uint32) & 0xFFFF).astype(np.int64)
     return np.abs(low - 0x8000) <= 4
 
