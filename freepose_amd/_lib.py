@@ -45,6 +45,11 @@ class ClipArch(C.Structure):
                 ("embed_dim", c_int), ("ln_eps", c_float), ("quick_gelu", c_int)]
 
 
+class ClipTextArch(C.Structure):
+    _fields_ = [("width", c_int), ("depth", c_int), ("heads", c_int), ("mlp_dim", c_int), ("vocab", c_int), ("ctx", c_int),
+                ("embed_dim", c_int), ("ln_eps", c_float)]
+
+
 # name -> (restype, argtypes); mirrors include/freepose_hip.h one to one
 SIGNATURES = {
     "fp_last_error": (c_char_p, []),
@@ -120,6 +125,12 @@ SIGNATURES = {
     "fp_op_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "fp_op_im2col_norm": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fp_op_attention_hd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "fp_op_attention_causal": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "fp_clip_text_create": (c_int, [c_void_p, P(ClipTextArch), P(c_void_p)]),
+    "fp_clip_text_destroy": (c_int, [c_void_p]),
+    "fp_clip_text_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p]),
+    "fp_clip_text_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "fp_clip_text_flops": (c_double, [c_void_p, c_int]),
     "fp_clip_create": (c_int, [c_void_p, P(ClipArch), P(c_void_p)]),
     "fp_clip_destroy": (c_int, [c_void_p]),
     "fp_clip_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p]),

@@ -1,8 +1,8 @@
-// Index arithmetic of attention_hd.hip and of the k-nearest-rows selection (retrieval.hip), kept free of device intrinsics so that a
-// host program can run it under the sanitizers (tools/attn_hd_host_check.cpp): supported shapes, the pad masks, the key-tile tail, the staging
-// and fragment offsets into the LDS images,
-// the row permutation that lines the first product's accumulators up with the second product's operand, and the tie rule of the
-// nearest-row order.
+// Index arithmetic of attention_hd.hip, attention_causal.hip and of the k-nearest-rows selection (retrieval.hip), kept free of device
+// intrinsics so that a host program can run it under the sanitizers (tools/attn_hd_host_check.cpp, tools/attn_causal_host_check.cpp):
+// supported shapes, the pad masks, the key-tile tail, the staging and fragment offsets into the LDS images,
+// the row permutation that lines the first product's accumulators up with the second product's operand, the tile walk and visibility
+// rule of the causal mask, and the tie rule of the nearest-row order.
 #pragma once
 #include <stdint.h>
 
@@ -50,6 +50,19 @@ FP_HD int fp_ahd_vstage_off(int c, int w) { return (fp_ahd_vstage_d0(c) + w) * F
 // 16-byte MFMA operand reads: K fragment fk, lane (li, lg), k step kk; V^T fragment fd, lane (li, lg), 32-key step ks
 FP_HD int fp_ahd_kfrag_off(int fk, int li, int lg, int kk, int kpitch) { return fp_ahd_tile_key(fk, li) * kpitch + lg * 16 + kk * 64; }
 FP_HD int fp_ahd_vfrag_off(int fd, int li, int lg, int ks) { return (16 * fd + li) * FP_AHD_V_PITCH + lg * 16 + ks * 64; }
+
+// ---- causal attention (attention_causal.hip): query t sees keys 0 .. t.  A workgroup owns FP_AHD_QUERY_BLOCK consecutive queries and
+// walks the key tiles from 0 up to the one that holds the last key any of its queries sees; tiles wholly above the diagonal are never
+// staged.  Pad queries (rows [n_tok, npad)) see every real key.
+#define FP_AHD_QUERY_BLOCK 64
+// key tiles the workgroup of queries [q0_block, q0_block + FP_AHD_QUERY_BLOCK) visits: 0 .. floor(min(q0_block + 63, n_tok - 1) / 64)
+FP_HD int fp_ahd_causal_num_tiles(int q0_block, int n_tok) {
+    const int last_q = q0_block + FP_AHD_QUERY_BLOCK - 1;
+    const int last_key = last_q < n_tok - 1 ? last_q : n_tok - 1;
+    return last_key / FP_AHD_KEY_TILE + 1;
+}
+// the logit (key, query) takes part in the softmax: a real key at or before the query
+FP_HD bool fp_ahd_causal_visible(int key, int query, int n_tok) { return fp_ahd_row_real(key, n_tok) && key <= query; }
 
 // ---- nearest rows: candidates are ordered by (squared distance ascending, row index ascending).  Distances are non-negative
 // floats, whose bit patterns order like the values, so one 64-bit integer carries the whole rule.

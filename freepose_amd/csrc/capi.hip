@@ -520,6 +520,10 @@ extern "C" int fp_op_attention_hd(const void* QKV, int ldqkv, void* O, int ldo, 
                                   float scale, void* stream) {
     return fp_attention_hd_fwd((const bf16_t*)QKV, ldqkv, (bf16_t*)O, ldo, B, heads, head_dim, n_tok, npad, scale, (hipStream_t)stream);
 }
+extern "C" int fp_op_attention_causal(const void* QKV, int ldqkv, void* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad,
+                                      float scale, void* stream) {
+    return fp_attention_causal_fwd((const bf16_t*)QKV, ldqkv, (bf16_t*)O, ldo, B, heads, head_dim, n_tok, npad, scale, (hipStream_t)stream);
+}
 extern "C" int fp_knn_l2(fp_ctx* ctx, const float* d_table, int N, int E, const float* d_queries, int Q, int k, int32_t* d_out_idx,
                          float* d_out_d2, void* stream) {
     FP_REQUIRE(ctx, "knn_l2: null context");

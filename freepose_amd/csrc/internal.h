@@ -52,6 +52,9 @@ int fp_attention_fwd(const bf16_t* QK, int ldqk, const bf16_t* Vt, bf16_t* O, in
 // attention_hd.hip: any head dimension (multiple of 8 up to 128) on the plain [q | k | v] output of one bias GEMM
 int fp_attention_hd_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
                         hipStream_t stream);
+// attention_causal.hip: the same layout and contract, query t attending to keys 0 .. t (the CLIP text tower)
+int fp_attention_causal_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
+                            hipStream_t stream);
 // vit_misc.hip
 // torchvision Normalize of the DINOv2 inputs (ImageNet); fp_im2col_norm_ms rounds mean / std to bf16 like its tensors in the image dtype
 constexpr float FP_IMAGENET_MEAN[3] = {0.485f, 0.456f, 0.406f}, FP_IMAGENET_SD[3] = {0.229f, 0.224f, 0.225f};

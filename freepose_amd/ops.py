@@ -883,6 +883,27 @@ def attention_hd(qkv: torch.Tensor, heads: int, n_tok: int, scale: Optional[floa
     return out
 
 
+def attention_causal(qkv: torch.Tensor, heads: int, n_tok: int, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attention_hd under a causal mask (fp_op_attention_causal, the attention of the CLIP text tower): the same arguments and layout;
+    token t attends to the tokens 0 .. t of its prompt."""
+    lib = _lib.load()
+    qkv = _dev(qkv, torch.bfloat16)
+    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads) != 0:
+        raise ValueError(f"attention_causal: qkv of shape {tuple(qkv.shape)} ([B, npad, 3*heads*hd]) with heads={heads}")
+    B, npad, w3 = qkv.shape
+    width = w3 // 3
+    hd = width // heads
+    if out is None:
+        out = torch.zeros((B, npad, width), dtype=torch.bfloat16, device=qkv.device)
+    else:
+        assert out.dtype == torch.bfloat16 and out.is_cuda and tuple(out.shape) == (B, npad, width)
+        assert out.stride(2) == 1 and out.stride(0) == npad * out.stride(1)
+    sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(hd))
+    check(lib.fp_op_attention_causal(ptr(qkv), w3, ptr(out), int(out.stride(1)), B, heads, hd, int(n_tok), npad, sc, current_stream()),
+          "fp_op_attention_causal")
+    return out
+
+
 def knn_l2(table: torch.Tensor, queries: torch.Tensor, k: int):
     """exact k nearest rows of `table` f32 [N,E] for each row of `queries` f32 [Q,E] in Euclidean distance (fp_knn_l2; the brute-force
     form of scipy.spatial.KDTree(table).query(queries, k)) -> (idx i32 [Q,k], squared distances f32 [Q,k]) ordered by (distance
@@ -997,6 +1018,116 @@ class ClipVisual:
     def __del__(self):
         try:
             self.lib.fp_clip_destroy(self.handle)
+        except Exception:
+            pass
+
+
+# ---- CLIP text tower (csrc/clip_text.hip) -------------------------------------------------------------
+CLIP_TEXT_ARCHS = {
+    # name: (width, depth, heads, mlp_dim, vocab, ctx, embed_dim) — the text half of open_clip's model configs (public); keyed by the
+    # name of the image tower it belongs to, head dimension 64 throughout
+    "ViT-bigG-14": (1280, 32, 20, 5120, 49408, 77, 1280),
+    "ViT-H-14": (1024, 24, 16, 4096, 49408, 77, 1024),
+    "ViT-L-14": (768, 12, 12, 3072, 49408, 77, 768),
+    # test towers: one per tiny image tower (its width, heads and embedding size; depth 2, 1024 tokens, 77 positions) ...
+    "tiny-64": (128, 2, 2, 512, 1024, 77, 64), "tiny-80": (320, 2, 4, 640, 1024, 77, 64), "tiny-104": (832, 2, 8, 1024, 1024, 77, 64),
+    "tiny-64-s56": (128, 2, 2, 512, 1024, 77, 64), "tiny-80-s56": (320, 2, 4, 640, 1024, 77, 64), "tiny-104-s56": (832, 2, 8, 1024, 1024, 77, 64),
+    "tiny-bigG-wide": (1280, 2, 20, 256, 1024, 77, 1280),
+    # ... a 17-position one (padded to 32 rows) and one block at ViT-bigG/14's text width
+    "tiny-64-c17": (128, 2, 2, 512, 1024, 17, 64),
+    "tiny-bigG-text": (1280, 1, 20, 256, 1024, 77, 1280),
+}
+
+
+def clip_text_state_dict_names(model_name: str) -> dict:
+    """open_clip text state-dict name -> shape (the top-level names of a CLIP checkpoint)"""
+    width, depth, heads, mlp, vocab, ctx, embed = CLIP_TEXT_ARCHS[model_name]
+    names = {"token_embedding.weight": (vocab, width), "positional_embedding": (ctx, width), "ln_final.weight": (width,),
+             "ln_final.bias": (width,), "text_projection": (width, embed)}
+    for i in range(depth):
+        p = f"transformer.resblocks.{i}."
+        names.update({p + "ln_1.weight": (width,), p + "ln_1.bias": (width,), p + "attn.in_proj_weight": (3 * width, width),
+                      p + "attn.in_proj_bias": (3 * width,), p + "attn.out_proj.weight": (width, width), p + "attn.out_proj.bias": (width,),
+                      p + "ln_2.weight": (width,), p + "ln_2.bias": (width,), p + "mlp.c_fc.weight": (mlp, width), p + "mlp.c_fc.bias": (mlp,),
+                      p + "mlp.c_proj.weight": (width, mlp), p + "mlp.c_proj.bias": (width,)})
+    return names
+
+
+def random_clip_text_state_dict(model_name: str, seed: int = 0) -> dict:
+    """seeded random-init weights under open_clip's text state-dict names (no checkpoint offline): trunc-normal linears and embeddings,
+    LayerNorm (1 + noise, noise)"""
+    width = CLIP_TEXT_ARCHS[model_name][0]
+    g = torch.Generator().manual_seed(seed)
+
+    def tn(shape, std=0.02):
+        return torch.nn.init.trunc_normal_(torch.empty(*shape), std=std, a=-2 * std, b=2 * std, generator=g)
+
+    sd = {}
+    for name, shape in clip_text_state_dict_names(model_name).items():
+        if name.endswith(("ln_final.weight", "ln_1.weight", "ln_2.weight")):
+            sd[name] = torch.ones(shape) + tn(shape, std=0.05)
+        elif name == "text_projection":
+            sd[name] = tn(shape, std=width ** -0.5)
+        elif name == "positional_embedding":
+            sd[name] = tn(shape, std=0.01)
+        else:
+            sd[name] = tn(shape)
+    return {k: v.to(torch.bfloat16) for k, v in sd.items()}
+
+
+class ClipText:
+    """Device-resident CLIP text tower (open_clip state-dict names) driving fp_clip_text_encode."""
+
+    def __init__(self, model_name: str = "ViT-bigG-14", state_dict: Optional[dict] = None, seed: int = 0, device: Optional[int] = None,
+                 chunk: int = 256):
+        if model_name not in CLIP_TEXT_ARCHS:
+            raise ValueError(f"unknown CLIP text model {model_name}")
+        self.width, self.depth, self.heads, self.mlp_dim, self.vocab, self.ctx, self.embed_dim = CLIP_TEXT_ARCHS[model_name]
+        self.model_name = model_name
+        self.chunk = int(chunk)
+        self.lib = _lib.load()
+        self.ctx_handle = context(device)
+        arch = _lib.ClipTextArch(self.width, self.depth, self.heads, self.mlp_dim, self.vocab, self.ctx, self.embed_dim, 1e-5)
+        h = C.c_void_p()
+        check(self.lib.fp_clip_text_create(self.ctx_handle, C.byref(arch), C.byref(h)), "fp_clip_text_create")
+        self.handle = h
+        self.weights = {}
+        self.load_state_dict(state_dict if state_dict is not None else random_clip_text_state_dict(model_name, seed))
+
+    def load_state_dict(self, sd: dict):
+        s = current_stream()
+        want = clip_text_state_dict_names(self.model_name)
+        missing = sorted(set(want) - set(sd))
+        if missing:
+            raise KeyError(f"CLIP text state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
+        for name in want:
+            w = _dev(torch.as_tensor(sd[name]), torch.bfloat16)
+            self.weights[name] = w  # keep alive: the library stores raw pointers
+            check(self.lib.fp_clip_text_set_weight(self.handle, name.encode(), ptr(w), w.numel(), s), f"set_weight({name})")
+        torch.cuda.synchronize()
+
+    def encode_text(self, ids: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
+        """token ids [N, ctx] (any integer dtype) -> bf16 [N, embed_dim], `chunk` prompts per tower call (bounded workspaces; a prompt's
+        embedding does not depend on the chunk it rides in).  An id outside [0, vocab) is an error."""
+        ids = torch.as_tensor(ids)
+        if ids.dim() != 2 or ids.shape[1] != self.ctx or ids.is_floating_point():
+            raise ValueError(f"CLIP text ids of shape {tuple(ids.shape)} {ids.dtype} (integer [N, {self.ctx}])")
+        x = ids.to("cuda", dtype=torch.int32).contiguous()
+        step = max(1, int(chunk or self.chunk))
+        out = torch.empty((x.shape[0], self.embed_dim), dtype=torch.bfloat16, device=x.device)
+        for i in range(0, x.shape[0], step):
+            part, dst = x[i:i + step], out[i:i + step]
+            check(self.lib.fp_clip_text_encode(self.handle, ptr(part), part.shape[0], ptr(dst), current_stream()), "fp_clip_text_encode")
+        return out
+
+    __call__ = encode_text
+
+    def flops(self, B: int) -> float:
+        return float(self.lib.fp_clip_text_flops(self.handle, int(B)))
+
+    def __del__(self):
+        try:
+            self.lib.fp_clip_text_destroy(self.handle)
         except Exception:
             pass
 

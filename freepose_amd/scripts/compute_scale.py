@@ -4,12 +4,13 @@ Drop-in for the reference CLI (scripts/compute_scale.py:15-63): proposals JSON i
 (`data/results/<dataset>/<props>_gpt4_scaled.json`) — the file scripts.dino_inference reads with `--depth_method zoedepth`.  Per
 image: 224 px crops of its proposals (bbox_extend 0.05) -> GPT4ScaleEstimator.estimate(proposals, entry['depth_pred'], K).
 
-The scale table is read from `--scale_feats` (default data/scale_feats.pt: {"feats", "scales"}); the reference computes it from
-data/gpt4_scales.json with the CLIP text tower, which is not provided here.  The predicted depth is the dataset entry's `depth_pred`
+The scale table is read from `--scale_feats` (default data/scale_feats.pt: {"feats", "scales"}).  The reference computes it from
+data/gpt4_scales.json with the CLIP text tower on every start (:28-29); `--scale_file data/gpt4_scales.json` does the same here
+(tokenizer merges: `--bpe_vocab` or FREEPOSE_CLIP_BPE) and writes the table to `--scale_feats` first.  The predicted depth is the dataset entry's `depth_pred`
 (BOPDataset: `<scene>/depth_pred/<frame>.png`, 16-bit / 65535).  An image without one is an error unless `--no_depth` is given; then
 the estimator runs without depth for every image (the table's medians, no correction).
 
-New flags: `--clip_model`, `--scale_feats`, `--allow_random_weights`, `--no_depth`, `--query_k`, `--gpus`.  Under a
+New flags: `--clip_model`, `--scale_feats`, `--scale_file`, `--bpe_vocab`, `--allow_random_weights`, `--no_depth`, `--query_k`, `--gpus`.  Under a
 torch.distributed.run launch the images are dealt round-robin over the ranks, the scales all-gathered, and rank 0 writes the file:
 the same bytes as one rank (an image's scales depend on that image only)."""
 from __future__ import annotations
@@ -56,7 +57,17 @@ def gather_scales(rows, n_total):
 
 
 def make_estimator(args):
-    clip = CLIPFeatureExtractor(args.clip_model, allow_random_weights=args.allow_random_weights or None)
+    """the extractor and the estimator on the table of `--scale_feats`.  With `--scale_file` the table is computed first, as the
+    reference does on every run (compute_scale.py:28-29): rank 0 runs the text tower over the file's names and writes `--scale_feats`,
+    the other ranks wait at a barrier; then every rank loads the same file."""
+    clip = CLIPFeatureExtractor(args.clip_model, allow_random_weights=args.allow_random_weights or None, bpe_vocab=args.bpe_vocab)
+    if args.scale_file is not None:
+        clip.require_text_tower()
+        rank, world = parallel.world()
+        if rank == 0:
+            GPT4ScaleEstimator.generate_clip_features(args.scale_file, clip, feats_path=args.scale_feats)
+        if world > 1:
+            torch.distributed.barrier()
     return GPT4ScaleEstimator(clip, query_k=args.query_k, feats_path=args.scale_feats)
 
 
@@ -65,6 +76,11 @@ def add_common_flags(ap):
     ap.add_argument("--clip_model", type=str, default="ViT-bigG-14", help="CLIP image tower (weights: FREEPOSE_CLIP_WEIGHTS)")
     ap.add_argument("--scale_feats", type=str, default="data/scale_feats.pt",
                     help="torch file {'feats': [N,E] text embeddings, 'scales': [N]} of the scale table (the text tower is not provided)")
+    ap.add_argument("--scale_file", type=str, default=None,
+                    help="JSON object {name: size} (the reference's data/gpt4_scales.json): compute the scale table with the CLIP text tower "
+                         "at start-up and write it to --scale_feats (needs a checkpoint with the text tensors and --bpe_vocab)")
+    ap.add_argument("--bpe_vocab", type=str, default=None,
+                    help="the tokenizer's merges file, open_clip's bpe_simple_vocab_16e6.txt.gz or its .txt (default: FREEPOSE_CLIP_BPE)")
     ap.add_argument("--allow_random_weights", action="store_true", help="run without the CLIP checkpoint (tests, benches)")
     ap.add_argument("--query_k", type=int, default=11, help="nearest table rows per crop (the reference's constant)")
     ap.add_argument("--gpus", type=int, default=1, help="self-launch N ranks, one per GPU")

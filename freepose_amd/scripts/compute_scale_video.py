@@ -10,7 +10,8 @@ Depth: the reference predicts each frame's depth with ZoeDepth, which is not pro
 one `<frame stem>.npy` per frame (float [H,W], metres) computed elsewhere; a relative path is looked up under the video's dataset
 directory first.  WITHOUT `--depth_dir` the estimator runs without depth: the median table size per crop, no depth correction.
 
-New flags: `--depth_dir`, `--clip_model`, `--scale_feats`, `--allow_random_weights`, `--query_k`, `--gpus`.  Under a
+New flags: `--depth_dir`, `--clip_model`, `--scale_feats`, `--scale_file` / `--bpe_vocab` (compute the scale table with the text tower
+first, see scripts.compute_scale), `--allow_random_weights`, `--query_k`, `--gpus`.  Under a
 torch.distributed.run launch the frames are dealt round-robin over the ranks (a frame's scales depend on that frame only), the
 scales all-gathered, and rank 0 takes the medians and writes the file: the same bytes as one rank."""
 from __future__ import annotations

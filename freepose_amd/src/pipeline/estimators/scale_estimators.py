@@ -123,7 +123,8 @@ class GPT4ScaleEstimator:
     of the same image is 1 -> / 2.  The embeddings (one tower call for all crops of the image: a crop's embedding does not depend on
     its batch), the nearest rows (ops.knn_l2, the brute-force form of the reference's KDTree query; exact ties in index order) and the
     depth-map scales run on the device; the medians are float64 on the host like the reference's.  The text embeddings are read from
-    `feats_path`: the text tower is not provided, so `scale_file` (which asks for them to be computed) is refused."""
+    `feats_path`, or with `scale_file` computed by the extractor's text tower first (generate_clip_features, which also writes them to
+    `feats_path`); an extractor without a text tower refuses `scale_file`."""
 
     def __init__(self, clip, query_k=11, scale_file=None, feats_path="data/scale_feats.pt", svd=True) -> None:
         import torch
@@ -175,7 +176,27 @@ class GPT4ScaleEstimator:
 
     @staticmethod
     def generate_clip_features(scale_file, clip, feats_path="data/scale_feats.pt"):
-        raise NotImplementedError("the CLIP text tower is not provided: compute the text embeddings of the scale table elsewhere and pass feats_path")
+        """reference :83-102: the names and sizes of `scale_file` (JSON object, in file order) -> tokenizer -> text tower -> each
+        embedding divided by its norm -> {"feats": float32 [N, E] on the CPU, "scales": float32 [N]}, saved to `feats_path` unless it
+        is None.  The reference runs the tower under fp16 autocast on a bf16 module; here it is the bf16 module regime of the image
+        side: bf16 forward, bf16 division by the bf16 norm (what `embed` does), then float."""
+        import json
+        import torch
+        if clip is None or not getattr(clip, "has_text_tower", False):
+            raise NotImplementedError("generate_clip_features needs a CLIP text tower: the extractor's weights hold no text tensors "
+                                      "(or no extractor was given); compute the scale table's embeddings elsewhere and pass feats_path")
+        with open(scale_file) as f:
+            gpt_scales = list(json.load(f).items())
+        object_names = [x[0] for x in gpt_scales]
+        scales = [x[1] for x in gpt_scales]
+        text = clip.tokenizer(object_names)
+        with torch.inference_mode():
+            text_features = clip.model.encode_text(text)
+            text_features = text_features / text_features.norm(dim=-1, keepdim=True)
+        feats_scales = {"feats": text_features.float().cpu(), "scales": torch.Tensor(scales)}
+        if feats_path is not None:
+            torch.save(feats_scales, feats_path)
+        return feats_scales
 
     @staticmethod
     def mask_to_bbox(mask):

@@ -334,8 +334,13 @@ int fp_op_im2col_norm(const void* d_img, void* d_A, int B, int H, int W, int ps,
  * the same rows of O receive finite values.  bf16 in / out, fp32 accumulation and softmax statistics, any sequence length. */
 int fp_op_attention_hd(const void* d_QKV, int ldqkv, void* d_O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
                        void* stream);
+/* the same layout and contract under a CAUSAL mask (open_clip's text transformer): query t attends to the real keys 0 .. t only.  Key
+ * tiles wholly above the diagonal are skipped; rows after the query inside a visited tile are loaded and weighted by exactly 0, so they
+ * must be finite for V (any bytes for pad rows [n_tok, npad), which are never read).  Pad query rows receive finite values. */
+int fp_op_attention_causal(const void* d_QKV, int ldqkv, void* d_O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
+                           void* stream);
 
-/* ---- CLIP image tower (src/pipeline/retrieval/clip.py: open_clip encode_image on a bf16 module) --------- */
+/* ---- CLIP image tower(src/pipeline/retrieval/clip.py: open_clip encode_image on a bf16 module) --------- */
 typedef struct fp_clip fp_clip;
 typedef struct {
     int width;      /* 1664 (ViT-bigG/14), 1280 (ViT-H/14), 1024 (ViT-L/14); a multiple of 64          */
@@ -360,6 +365,30 @@ int fp_clip_set_weight(fp_clip* clip, const char* name, const void* d_tensor, si
  * conv (no bias), [class; patches] + positional embedding, ln_pre, the blocks, ln_post on the class row, projection. */
 int fp_clip_encode_image(fp_clip* clip, const void* d_images, int B, int S, void* d_out, void* stream);
 double fp_clip_flops(const fp_clip* clip, int B);
+
+/* ---- CLIP text tower (scale_estimators.py:91-94: open_clip encode_text on a bf16 module) ---------------- */
+typedef struct fp_clip_text fp_clip_text;
+typedef struct {
+    int width;      /* 1280 (ViT-bigG/14), 1024 (ViT-H/14), 768 (ViT-L/14); a multiple of 64           */
+    int depth;      /* 32 / 24 / 12                                                                    */
+    int heads;      /* 20 / 16 / 12: head dimension width / heads (64), a multiple of 8 up to 128      */
+    int mlp_dim;    /* 5120 / 4096 / 3072                                                              */
+    int vocab;      /* 49408                                                                           */
+    int ctx;        /* 77 tokens per prompt (padded to a multiple of 16 rows internally)               */
+    int embed_dim;  /* 1280 / 1024 / 768                                                               */
+    float ln_eps;   /* 1e-5                                                                            */
+} fp_clip_text_arch;
+int fp_clip_text_create(fp_ctx* ctx, const fp_clip_text_arch* arch, fp_clip_text** out);
+int fp_clip_text_destroy(fp_clip_text* text);
+/* Register one tensor (bf16, device) by its open_clip state-dict name: token_embedding.weight [vocab, width], positional_embedding
+ * [ctx, width], transformer.resblocks.{i}.* as for the image tower, ln_final.{weight,bias}, text_projection ([width, embed_dim], applied
+ * as x @ P).  text_projection is copied (transposed); every other tensor is referenced and must outlive the handle. */
+int fp_clip_text_set_weight(fp_clip_text* text, const char* name, const void* d_tensor, size_t numel, void* stream);
+/* d_ids i32 [B, ctx] -> d_out bf16 [B, embed_dim]: token + positional embedding, the blocks under the causal mask, ln_final on the row
+ * of the largest id of each prompt (the first one: the end-of-text token), projection.  An id outside [0, vocab) is refused
+ * (FP_ERR_INVALID; the embedding table is never read out of range).  Synchronises the stream once, after the embedding gather. */
+int fp_clip_text_encode(fp_clip_text* text, const int32_t* d_ids, int B, void* d_out, void* stream);
+double fp_clip_text_flops(const fp_clip_text* text, int B);
 
 /* ---- exact k nearest rows (scipy.spatial.KDTree.query of GPT4ScaleEstimator, scale_estimators.py:48,66) -- */
 /* d_table f32 [N,E], d_queries f32 [Q,E] -> d_out_idx i32 [Q,k], d_out_d2 f32 [Q,k] (SQUARED Euclidean distances, fp32, fixed
