@@ -141,6 +141,8 @@ SIGNATURES = {
     "fp_pnp_epnp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "fp_video_errors": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
+    "fp_bop_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fp_timer_create": (c_int, [P(c_void_p)]),
     "fp_timer_start": (c_int, [c_void_p, c_void_p]),
     "fp_timer_stop": (c_int, [c_void_p, c_void_p]),

@@ -388,6 +388,27 @@ extern "C" int fp_video_errors(fp_ctx* ctx, const double* d_est, const double* d
 }
 
 // ---------------------------------------------------------------------------------------------
+// BOP pose matching and recall counts (bop_score.hip).  Every table is device memory: the sizes are checked here, the contents by the
+// caller on the tables' host twins (ops.bop_scores); the kernel skips a group whose row reaches outside the tables.
+extern "C" int fp_bop_scores(fp_ctx* ctx, const double* d_err, const int32_t* d_groups, const uint8_t* d_gt_valid, const int32_t* d_gt_obj,
+                             const int32_t* d_gt_scene, const double* d_th, int P, int Gr, int R, int T, int n_obj, int n_scene, int n_top,
+                             int32_t* d_match, int32_t* d_tp_obj, int32_t* d_tp_scene, int32_t* d_tar_obj, int32_t* d_tar_scene,
+                             void* stream) {
+    FP_REQUIRE(ctx && d_th && d_tp_obj && d_tp_scene && d_tar_obj && d_tar_scene, "bop_scores: null argument");
+    FP_REQUIRE(T >= 1 && T <= 65536, "bop_scores: T=%d thresholds (1..65536)", T);
+    FP_REQUIRE(P >= 0 && Gr >= 0 && R >= 0, "bop_scores: P=%d errors, Gr=%d groups, R=%d ground truths (>= 0)", P, Gr, R);
+    FP_REQUIRE(n_obj >= 1 && n_scene >= 1, "bop_scores: n_obj=%d, n_scene=%d (>= 1)", n_obj, n_scene);
+    FP_REQUIRE((int64_t)Gr * T <= INT32_MAX && (int64_t)R * T <= INT32_MAX && (int64_t)n_obj * T <= INT32_MAX &&
+                   (int64_t)n_scene * T <= INT32_MAX,
+               "bop_scores: Gr=%d, R=%d, n_obj=%d, n_scene=%d times T=%d (each product below 2^31)", Gr, R, n_obj, n_scene, T);
+    FP_REQUIRE(P == 0 || d_err, "bop_scores: null d_err with P=%d", P);
+    FP_REQUIRE(Gr == 0 || d_groups, "bop_scores: null d_groups with Gr=%d", Gr);
+    FP_REQUIRE(R == 0 || (d_gt_valid && d_gt_obj && d_gt_scene && d_match), "bop_scores: null ground-truth table or d_match with R=%d", R);
+    return fp_bop_scores_launch(d_err, d_groups, d_gt_valid, d_gt_obj, d_gt_scene, d_th, P, Gr, R, T, n_obj, n_scene, n_top, d_match,
+                                d_tp_obj, d_tp_scene, d_tar_obj, d_tar_scene, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
 // kernel-level entry points
 // (the GEMM entries are the driver's own steps of tower_steps.h with the caller's leading dimensions; fp_ctx::gemm launches them)
 extern "C" int fp_op_gemm(fp_ctx* ctx, const void* X, int ldx, const void* W, int ldw, void* Cc, int ldc, const void* bias,

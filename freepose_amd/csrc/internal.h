@@ -118,3 +118,7 @@ int fp_pnp_epnp_launch(const double* pts3d, const double* pts2d, const uint8_t* 
 // fp_video_errors' host tables; aligned [M,Nmax,3], frames [M,Nmax,FP_VE_FRAME_LD]; pairs_out may be null
 int fp_video_errors_launch(const double* est, const double* gt, const int* meta, const double* params, int M, int Nmax, int D,
                            double* aligned, double* frames, double* per_offset, double* final_out, double* pairs_out, hipStream_t s);
+// bop_score.hip: BOP pose matching and recall counts for all thresholds at once (bop_score_core.h holds the host-checkable steps)
+int fp_bop_scores_launch(const double* err, const int32_t* groups, const uint8_t* gt_valid, const int32_t* gt_obj, const int32_t* gt_scene,
+                         const double* th, int P, int Gr, int R, int T, int n_obj, int n_scene, int n_top, int32_t* match, int32_t* tp_obj,
+                         int32_t* tp_scene, int32_t* tar_obj, int32_t* tar_scene, hipStream_t s);

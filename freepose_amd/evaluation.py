@@ -8,6 +8,10 @@ integer pixel counts / float64 distances; the error values are formed below in f
 
 Numerics (DESIGN.md "Scoring"): cus / vsd are integer-exact given the same depth images; chamfer / chamfer_proj are within
 2e-6 (r + e) of the kd-tree result; re / te are the reference's host expressions.
+
+The second half turns those errors into scores: `BopScorer` packs the groups of an errors directory once and matches estimates to ground
+truths and counts recalls for all thresholds in one device call (fp_bop_scores; eval_calc_scores.py:188-290, pose_matching.py, score.py;
+DESIGN.md §16), exactly.
 """
 from __future__ import annotations
 
@@ -200,3 +204,175 @@ class PoseErrorEvaluator:
                 c = ops.depth_compare(d_est, d_gt, dt, idx[b0:b1], np.stack(Ks[b0:b1]), float(vsd_delta), taus, div[b0:b1]).cpu().numpy()
                 out += [vsd_from_counts(r[2], r[3], r[4:]) for r in c]
         return out
+
+
+# ---- BOP scores: matching, recalls (csrc/bop_score.hip) --------------------------------------------------------------------------------
+BOP_NORMALIZED_BY_DIAMETER = ("ad", "add", "adi", "mssd", "chamfer")       # eval_calc_scores.py:55,57
+BOP_NORMALIZED_BY_IM_WIDTH = ("mspd", "chamfer_proj")
+
+
+def score_signature(correct_th, visib_gt_min) -> str:
+    """misc.get_score_signature"""
+    return "th=" + "-".join("{:.3f}".format(t) for t in correct_th) + "_min-visib={:.3f}".format(visib_gt_min)
+
+
+def bop_json_text(content) -> str:
+    """the text inout.save_json writes: a dict with its top-level keys sorted, one per line; a list with one record per line; inner
+    values through json.dumps(sort_keys=True)"""
+    import json
+    if isinstance(content, dict):
+        items = sorted(content.items(), key=lambda x: x[0])
+        return "{\n" + ",\n".join('  "{}": {}'.format(k, json.dumps(v, sort_keys=True)) for k, v in items) + ("\n" if items else "") + "}"
+    if isinstance(content, list):
+        return "[\n" + ",\n".join("  {}".format(json.dumps(e, sort_keys=True)) for e in content) + ("\n" if content else "") + "]"
+    return json.dumps(content, sort_keys=True)
+
+
+def bop_gt_valid(im_gt, im_gt_info, im_targets, visib_gt_min) -> list:
+    """which ground truths of one image may be matched (eval_calc_scores.py:225-253).  im_targets: obj_id -> target of the image."""
+    if visib_gt_min >= 0:
+        return [bool(gt["obj_id"] in im_targets and im_gt_info[gt_id]["visib_fract"] >= visib_gt_min) for gt_id, gt in enumerate(im_gt)]
+    valid = [False] * len(im_gt)
+    to_add = {obj_id: trg["inst_count"] for obj_id, trg in im_targets.items()}
+    for gt_id in sorted(range(len(im_gt)), key=lambda i: im_gt_info[i]["visib_fract"], reverse=True):   # stable: ties keep gt_id order
+        obj_id = im_gt[gt_id]["obj_id"]
+        if to_add.get(obj_id, 0) > 0:
+            valid[gt_id] = True
+            to_add[obj_id] -= 1
+    return valid
+
+
+def _recall(tp_count, targets_count) -> float:
+    """score.py calc_recall"""
+    return 0.0 if targets_count == 0 else tp_count / float(targets_count)
+
+
+class BopScorer:
+    """The matching and scoring of bop_toolkit/scripts/eval_calc_scores.py:188-290 for all thresholds in one device call.
+
+    targets: the list of the targets file; scene_gt / scene_gt_info: scene_id -> im_id -> list per ground truth (integer keys; only
+    "obj_id" and "visib_fract" are read); obj_ids / scene_ids: the objects and scenes the recalls are listed for.  The groups — one per
+    (scene, image, target object with a ground truth in the image) — and the validity of every ground truth are built once, here; no
+    file is read."""
+
+    def __init__(self, targets, scene_gt, scene_gt_info, obj_ids, scene_ids, visib_gt_min=-1):
+        self.obj_ids, self.scene_ids = [int(i) for i in obj_ids], [int(i) for i in scene_ids]
+        self.visib_gt_min = float(visib_gt_min)
+        obj_index = {o: k for k, o in enumerate(self.obj_ids)}
+        scene_index = {s: k for k, s in enumerate(self.scene_ids)}
+        targets_org = {}
+        for t in targets:
+            targets_org.setdefault(t["scene_id"], {}).setdefault(t["im_id"], {})[t["obj_id"]] = t
+        self.records = []         # the reference's match records before matching, in its order: scene, image (targets order), gt_id
+        self.groups = []          # (scene_id, im_id, obj_id, [record index per ground truth, ascending gt_id], obj index, scene index)
+        for scene_id, scene_targets in targets_org.items():
+            for im_id, im_targets in scene_targets.items():
+                im_gt = scene_gt[scene_id][im_id]
+                valid = bop_gt_valid(im_gt, scene_gt_info[scene_id][im_id], im_targets, self.visib_gt_min)
+                row0 = len(self.records)
+                by_obj = {}
+                for gt_id, gt in enumerate(im_gt):
+                    self.records.append({"scene_id": scene_id, "im_id": im_id, "obj_id": gt["obj_id"], "gt_id": gt_id, "est_id": -1,
+                                         "score": -1, "error": -1, "error_norm": -1, "valid": valid[gt_id]})
+                    by_obj.setdefault(gt["obj_id"], []).append(row0 + gt_id)
+                    if valid[gt_id] and (gt["obj_id"] not in obj_index or scene_id not in scene_index):
+                        raise ValueError(f"scene {scene_id}, image {im_id}: the valid ground truth {gt_id} of object {gt['obj_id']} is "
+                                         f"outside the object list {self.obj_ids} or the scene list {self.scene_ids}")
+                for obj_id, rows in by_obj.items():
+                    if obj_id not in im_targets or obj_id not in obj_index or scene_id not in scene_index:
+                        continue          # no ground truth of it is valid: nothing can match and there is no target
+                    self.groups.append((scene_id, im_id, obj_id, rows, obj_index[obj_id], scene_index[scene_id]))
+
+    # ---- host packing ------------------------------------------------------------------------------------------------------------------
+    def pack(self, scene_errs_by_scene, n_top, diameters=None, im_width=None) -> dict:
+        """the tables of fp_bop_scores (numpy) + what is needed to read its answer back: `row_record` [R] record index of each table row,
+        `ests` per group the estimates in matching order, each (record of the errors file, normalised errors per column)."""
+        org = {}
+        for scene_id, errs in scene_errs_by_scene.items():
+            for e in errs:
+                org.setdefault((scene_id, e["im_id"], e["obj_id"]), []).append(e)
+        factor = None if im_width is None else 640.0 / float(im_width)
+        err, groups, row_record, gt_obj, gt_scene, ests_out = [], [], [], [], [], []
+        in_group = np.zeros(len(self.records), bool)
+        for scene_id, im_id, obj_id, rows, oi, si in self.groups:
+            gt_ids = [self.records[r]["gt_id"] for r in rows]
+            ests = org.get((scene_id, im_id, obj_id), [])
+            cols = gt_ids
+            if ests:
+                keys = [int(k) for k in ests[0]["errors"]]
+                for e in ests:
+                    if [int(k) for k in e["errors"]] != keys:
+                        raise ValueError(f"scene {scene_id}, image {im_id}, object {obj_id}: estimate {e['est_id']} lists the ground truths "
+                                         f"{list(e['errors'])}, the group's first estimate {keys} (one visiting order per group)")
+                if len(set(keys)) != len(keys) or not set(keys) <= set(gt_ids):
+                    raise ValueError(f"scene {scene_id}, image {im_id}, object {obj_id}: errors against the ground truths {keys}; the "
+                                     f"object's ground truths in this image are {gt_ids}")
+                cols = keys + [g for g in gt_ids if g not in keys]            # a ground truth without an error can never match: NaN
+            ests = sorted(ests, key=lambda e: e["score"], reverse=True)       # stable: ties keep the file's order
+            if n_top > 0:
+                ests = ests[:n_top]
+            packed = []
+            for e in ests:
+                vals = list(e["errors"].values())
+                if any(len(v) != 1 for v in vals):
+                    raise ValueError(f"scene {scene_id}, image {im_id}, object {obj_id}: an error with {len(vals[0])} elements; only "
+                                     "one-element errors are scored here (rete needs two thresholds)")
+                x = [v[0] for v in vals]
+                if diameters is not None:
+                    d = float(diameters[e["obj_id"]])
+                    x = [v / d for v in x]
+                if factor is not None:
+                    x = [factor * v for v in x]
+                packed.append((e, x))
+                err.extend(x + [float("nan")] * (len(cols) - len(x)))
+            groups.append((len(err) - len(ests) * len(cols), len(ests), len(cols), len(row_record)))
+            row0 = rows[0] - gt_ids[0]
+            for g in cols:
+                row_record.append(row0 + g)
+                in_group[row0 + g] = True
+            gt_obj += [oi] * len(cols)
+            gt_scene += [si] * len(cols)
+            ests_out.append(packed)
+        rest = np.flatnonzero(~in_group)          # ground truths of non-target objects: rows of no group, never valid
+        row_record = np.asarray(row_record + rest.tolist(), np.int64)
+        return {"err": np.asarray(err, np.float64), "groups": np.asarray(groups, np.int32).reshape(-1, 4),
+                "gt_valid": np.asarray([self.records[r]["valid"] for r in row_record], np.uint8),
+                "gt_obj": np.asarray(gt_obj + [0] * len(rest), np.int32), "gt_scene": np.asarray(gt_scene + [0] * len(rest), np.int32),
+                "row_record": row_record, "ests": ests_out, "n_top": int(n_top)}
+
+    def unpack(self, tables, thresholds, match, tp_obj, tp_scene, tar_obj, tar_scene) -> list:
+        """the answer of fp_bop_scores (host arrays) -> [(scores dict, match records)] per threshold, the reference's keys and values"""
+        out = []
+        tars = int(tar_obj.sum())
+        row_record = tables["row_record"].tolist()
+        row_group = {}                                       # table row -> (the group's estimates, column)
+        for (off, E, G, first), ests in zip(tables["groups"].tolist(), tables["ests"]):
+            for c in range(G):
+                row_group[first + c] = (ests, c)
+        for ti, th in enumerate(thresholds):
+            records = [dict(r) for r in self.records]
+            for row in np.flatnonzero(match[ti] >= 0).tolist():
+                ests, c = row_group[row]
+                e, x = ests[int(match[ti, row])]
+                records[row_record[row]].update(est_id=e["est_id"], score=e["score"], error=[x[c]], error_norm=[x[c] / float(th)])
+            tps = int(tp_obj[ti].sum())
+            obj_recalls = {o: _recall(int(tp_obj[ti, k]), int(tar_obj[k])) for k, o in enumerate(self.obj_ids)}
+            scene_recalls = {s: float(_recall(int(tp_scene[ti, k]), int(tar_scene[k]))) for k, s in enumerate(self.scene_ids)}
+            scores = {"recall": float(_recall(tps, tars)), "obj_recalls": obj_recalls,
+                      "mean_obj_recall": float(np.mean(list(obj_recalls.values())).squeeze()), "scene_recalls": scene_recalls,
+                      "mean_scene_recall": float(np.mean(list(scene_recalls.values())).squeeze()), "gt_count": len(records),
+                      "targets_count": tars, "tp_count": tps}
+            out.append((scores, records))
+        return out
+
+    def scores(self, scene_errs_by_scene, error_type, thresholds, n_top, diameters=None, im_width=None) -> list:
+        """scene_errs_by_scene: scene_id -> the list of an errors_<scene>.json; thresholds: one number per score to compute; diameters
+        {obj_id: diameter} / im_width are given when the error type is normalised by them (e / diameter, e * (640.0 / im_width), in
+        fp64 on the host, before matching).  One device call for all thresholds -> [(scores dict, match records)] per threshold."""
+        if error_type == "rete":
+            raise ValueError("rete has two thresholds per score; only one-element errors are scored here")
+        thresholds = [float(t) for t in thresholds]
+        tables = self.pack(scene_errs_by_scene, int(n_top), diameters, im_width)
+        res = ops.bop_scores(tables["err"], tables["groups"], tables["gt_valid"], tables["gt_obj"], tables["gt_scene"], thresholds,
+                             len(self.obj_ids), len(self.scene_ids), int(n_top))
+        return self.unpack(tables, thresholds, *[r.cpu().numpy() for r in res])

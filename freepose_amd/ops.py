@@ -649,6 +649,78 @@ def video_errors(est, gt, dts, est_scale, gt_scale, w, h, video=None, n_frames=N
     return out
 
 
+# ---- BOP scores: pose matching and recall counts (csrc/bop_score.hip) -------------------------------
+BOP_GROUP_LD = 4                                           # csrc/bop_score_core.h FP_BS_GROUP_LD: {err_offset, E, G, first_gt_row}
+BOP_MAX_THRESHOLDS = 65536
+
+
+def bop_tables_check(err, groups, gt_valid, gt_obj, gt_scene, th, n_obj, n_scene):
+    """The limits of fp_bop_scores on the host twins of its tables (numpy only, no device): returns them as contiguous arrays of the
+    entry's types, or raises ValueError with the offending group."""
+    err = np.ascontiguousarray(err, dtype=np.float64).reshape(-1)
+    groups = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1, BOP_GROUP_LD)
+    gt_valid = np.ascontiguousarray(gt_valid, dtype=np.uint8).reshape(-1)
+    gt_obj = np.ascontiguousarray(gt_obj, dtype=np.int32).reshape(-1)
+    gt_scene = np.ascontiguousarray(gt_scene, dtype=np.int32).reshape(-1)
+    th = np.ascontiguousarray(th, dtype=np.float64).reshape(-1)
+    P, Gr, R, T = len(err), len(groups), len(gt_valid), len(th)
+    if not 1 <= T <= BOP_MAX_THRESHOLDS:
+        raise ValueError(f"bop_scores: T={T} thresholds (1..{BOP_MAX_THRESHOLDS})")
+    if int(n_obj) < 1 or int(n_scene) < 1:
+        raise ValueError(f"bop_scores: n_obj={n_obj}, n_scene={n_scene} (>= 1)")
+    if len(gt_obj) != R or len(gt_scene) != R:
+        raise ValueError(f"bop_scores: gt_valid [{R}], gt_obj [{len(gt_obj)}], gt_scene [{len(gt_scene)}] (one row per ground truth)")
+    if max(Gr, R, int(n_obj), int(n_scene)) * T >= 2 ** 31 or P >= 2 ** 31:
+        raise ValueError(f"bop_scores: Gr={Gr}, R={R}, n_obj={n_obj}, n_scene={n_scene} times T={T}, and P={P} (each below 2^31)")
+    g = groups.astype(np.int64)
+    off, E, G, first = g[:, 0], g[:, 1], g[:, 2], g[:, 3]
+    bad = np.flatnonzero((off < 0) | (E < 0) | (G < 0) | (first < 0) | (off + E * G > P) | (first + G > R))
+    if len(bad):
+        i = int(bad[0])
+        raise ValueError(f"bop_scores: group {i} = {groups[i].tolist()} reaches outside P={P} errors or R={R} ground truths")
+    rows = np.flatnonzero(G > 0)
+    rows = rows[np.argsort(first[rows], kind="stable")]
+    over = np.flatnonzero(first[rows][:-1] + G[rows][:-1] > first[rows][1:])
+    if len(over):
+        a, b = int(rows[over[0]]), int(rows[over[0] + 1])
+        raise ValueError(f"bop_scores: groups {a} and {b} share ground-truth rows ({groups[a].tolist()}, {groups[b].tolist()})")
+    if len(rows):
+        Gs, fs = G[rows], first[rows]
+        idx = np.repeat(fs, Gs) + (np.arange(int(Gs.sum())) - np.repeat(np.cumsum(Gs) - Gs, Gs))
+        for name, col, n in (("gt_obj", gt_obj, int(n_obj)), ("gt_scene", gt_scene, int(n_scene))):
+            head = np.repeat(col[fs], Gs)
+            wrong = np.flatnonzero((col[idx] != head) | (head < 0) | (head >= n))
+            if len(wrong):
+                r = int(idx[wrong[0]])
+                raise ValueError(f"bop_scores: {name}[{r}] = {int(col[r])} (one index in 0..{n - 1} for all rows of a group)")
+    return err, groups, gt_valid, gt_obj, gt_scene, th
+
+
+def bop_scores(err, groups, gt_valid, gt_obj, gt_scene, th, n_obj: int, n_scene: int, n_top: int = 0):
+    """Pose matching and recall counts of the BOP toolkit (pose_matching.py match_poses :39-87, score.py :77-109) for every group and all
+    T thresholds in one launch.  Host tables (numpy): err f64 [P] (per group a row-major [E,G] block, estimates in matching order and cut to
+    n_top, ground truths in visiting order, already normalised), groups i32 [Gr,4] = {err_offset, E, G, first_gt_row}, gt_valid u8 [R],
+    gt_obj / gt_scene i32 [R] indices into the object / scene lists, th f64 [T]; n_top > 0 caps the targets of a group.  The tables are
+    checked (bop_tables_check: ValueError with a message, nothing is launched) and uploaded.
+    -> device tensors (match i32 [T,R]: row of the matched estimate within its group or -1, tp_obj i32 [T,n_obj], tp_scene i32 [T,n_scene],
+    tar_obj i32 [n_obj], tar_scene i32 [n_scene]).  Comparisons and integer sums only: exact, and two calls give the same bits."""
+    err, groups, gt_valid, gt_obj, gt_scene, th = bop_tables_check(err, groups, gt_valid, gt_obj, gt_scene, th, n_obj, n_scene)
+    lib = _lib.load()
+    P, Gr, R, T = len(err), len(groups), len(gt_valid), len(th)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a: torch.from_numpy(a).to(dev) if a.size else None   # noqa: E731  (an empty tensor has no address to pass)
+    d_err, d_groups, d_valid, d_obj, d_scene, d_th = up(err), up(groups), up(gt_valid), up(gt_obj), up(gt_scene), up(th)
+    match = torch.empty((T, R), dtype=torch.int32, device=dev)
+    tp_obj = torch.empty((T, int(n_obj)), dtype=torch.int32, device=dev)
+    tp_scene = torch.empty((T, int(n_scene)), dtype=torch.int32, device=dev)
+    tar_obj = torch.empty((int(n_obj),), dtype=torch.int32, device=dev)
+    tar_scene = torch.empty((int(n_scene),), dtype=torch.int32, device=dev)
+    check(lib.fp_bop_scores(context(), ptr(d_err), ptr(d_groups), ptr(d_valid), ptr(d_obj), ptr(d_scene), ptr(d_th), P, Gr, R, T, int(n_obj),
+                            int(n_scene), int(n_top), ptr(match) if R else None, ptr(tp_obj), ptr(tp_scene), ptr(tar_obj), ptr(tar_scene),
+                            current_stream()), "fp_bop_scores")
+    return match, tp_obj, tp_scene, tar_obj, tar_scene
+
+
 # ---- pose-error evaluation (csrc/eval.hip) ----------------------------------------------------------
 EVAL_XF_LD, EVAL_TABLE_LD, EVAL_MAX_TAUS = 40, 8, 16      # csrc/internal.h FP_EVAL_*
 EVAL_MAX_PAIRS = 65535                                     # pairs per launch (grid z / y)

@@ -5,7 +5,8 @@ Counterpart of bop_toolkit/scripts/eval_calc_errors.py for the model-free errors
 (scene_id,im_id,obj_id,score,R,t,bbox_visib,scale,time — inout.load_bop_results_bbox_visib, :297-347) and the BOP dataset as it is on
 disk (scene_gt.json, scene_gt_info.json, scene_camera.json, the targets JSON, models_eval/obj_*.ply + models_info.json, depth PNG x
 depth_scale), and writes `errors_<scene>.json` files with the keys and under the path template the reference uses
-(eval_calc_errors.py:72-74,571-579,592-624), so the toolkit's eval_calc_scores.py takes them unchanged.
+(eval_calc_errors.py:72-74,571-579,592-624), so `scripts.eval_calc_scores` / `scripts.eval_bop19_pose` of this package — or the
+toolkit's eval_calc_scores.py — take them unchanged.
 
 What is kept from the reference script:
   * the flag names and their defaults (`--renderer_type` is accepted with any value: the depth images always come from the HIP
@@ -15,7 +16,8 @@ What is kept from the reference script:
   * `--skip_missing` / `--vsd_normalized_by_diameter` are bool(<string>) as there: any non-empty value is true;
   * SLURM_ARRAY_TASK_ID selects one scene (:233-239, index into the scenes of the targets file in file order); unset = all scenes.
 The work of a scene is batched: the estimate x ground-truth pairs of many images go through freepose_amd.evaluation.PoseErrorEvaluator
-in a few launches instead of one render pair / two kd-trees per pair.  Score aggregation (eval_calc_scores.py) is not part of this.
+in a few launches instead of one render pair / two kd-trees per pair.  Matching and recalls: `scripts.eval_calc_scores`; the whole
+table of the paper in one process: `scripts.eval_bop19_pose`.
 """
 from __future__ import annotations
 

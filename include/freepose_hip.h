@@ -454,6 +454,30 @@ int fp_pnp_epnp(fp_ctx* ctx, const double* d_pts3d, const double* d_pts2d, const
 int fp_video_errors(fp_ctx* ctx, const double* d_est, const double* d_gt, const int32_t* h_meta, const double* h_params, int M, int V,
                     int Nmax, int D, double* d_per_offset, double* d_final, double* d_aligned, double* d_pairs, void* stream);
 
+/* ---- BOP scores: pose matching and recall counts for all thresholds at once --------------------------------- */
+/* Replaces the per-threshold work of bop_toolkit/scripts/eval_calc_scores.py:275-290, i.e. bop_toolkit_lib/pose_matching.py match_poses
+ * (:39-87, one-element errors) under match_poses_scene (:115-159) and the counting of score.py calc_localization_scores (:77-109), which
+ * scripts/eval_bop19_pose.py:217-252 runs in one process per (error type, threshold).  One call matches every (scene, image, object)
+ * group of an errors directory under all T thresholds.  All tables are DEVICE memory, packed by the host (freepose_amd.evaluation):
+ *   d_err      f64 [P]     per group a row-major [E,G] block: rows = the group's estimates in matching order (score descending, ties in
+ *                          file order, already cut to n_top), columns = its ground truths in visiting order; already normalised
+ *   d_groups   i32 [Gr,4]  {err_offset, E, G, first_gt_row}; E = 0 and G = 0 are legal; the ranges [first_gt_row, + G) are disjoint
+ *   d_gt_valid u8  [R]     1 = the ground truth may be matched and counts as a target
+ *   d_gt_obj   i32 [R], d_gt_scene i32 [R]  index into the object / scene list (one object and one scene per group; rows outside every
+ *                          group are not read and are never matched)
+ *   d_th       f64 [T]     thresholds of correctness
+ * Per group and threshold: each estimate in turn takes the valid, not yet matched ground truth with the lowest error < th (strict; NaN
+ * never matches; equal errors go to the column visited first): the reference's greedy assignment, not an optimal one.
+ * -> d_match i32 [T,R] row (within its group) of the estimate matched to each ground truth, or -1; d_tp_obj i32 [T,n_obj] and d_tp_scene
+ * i32 [T,n_scene] matched ground truths; d_tar_obj i32 [n_obj] and d_tar_scene i32 [n_scene] targets = valid ground truths per group,
+ * at most n_top of them when n_top > 0 (they do not depend on the threshold).
+ * Refused with FP_ERR_INVALID and a message before anything is launched: T < 1, negative sizes, n_obj or n_scene < 1, a product with T
+ * at or above 2^31, a null table of non-zero size.  A group whose row reaches outside P or R is skipped on the device.
+ * Comparisons and integer atomics only: exact, and two calls give the same bits. */
+int fp_bop_scores(fp_ctx* ctx, const double* d_err, const int32_t* d_groups, const uint8_t* d_gt_valid, const int32_t* d_gt_obj,
+                  const int32_t* d_gt_scene, const double* d_th, int P, int Gr, int R, int T, int n_obj, int n_scene, int n_top,
+                  int32_t* d_match, int32_t* d_tp_obj, int32_t* d_tp_scene, int32_t* d_tar_obj, int32_t* d_tar_scene, void* stream);
+
 /* ---- measurement helpers (bench.py: HIP-event timing on the launch stream) ----------------------------- */
 int fp_timer_create(void** out);
 int fp_timer_start(void* timer, void* stream);
