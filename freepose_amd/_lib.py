@@ -143,6 +143,9 @@ SIGNATURES = {
                                 c_void_p, c_void_p]),
     "fp_bop_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fp_gt_visibility": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fp_pts_diameter": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "fp_timer_create": (c_int, [P(c_void_p)]),
     "fp_timer_start": (c_int, [c_void_p, c_void_p]),
     "fp_timer_stop": (c_int, [c_void_p, c_void_p]),

@@ -7,6 +7,7 @@
 #include "tower_steps.h"
 #include "pnp_core.h"
 #include "video_eval_core.h"
+#include "gt_info_core.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -284,6 +285,51 @@ extern "C" int fp_depth_compare(fp_ctx* ctx, const float* d_depth_est, const flo
     }
     return fp_depth_compare_launch(d_depth_est, d_depth_gt, B, Hh, W, d_depth_test, n_img, d_img_idx, d_params, d_taus, n_tau, d_out,
                                    (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ground-truth visibility, masks, boxes and model diameters (gt_info.hip).  d_img_idx and d_ranges are small device tables: they are
+// copied to the host and checked with gt_info_core.h's predicates before anything is launched (one stream synchronisation per call).
+extern "C" int fp_gt_visibility(fp_ctx* ctx, const float* d_depth_gt, int B, int Hr, int Wr, int ox, int oy, const float* d_depth_test,
+                                int n_img, int H, int W, const int32_t* d_img_idx, const double* d_params, uint8_t* d_mask,
+                                uint8_t* d_mask_visib, int32_t* d_out, void* stream) {
+    FP_REQUIRE(ctx, "gt_visibility: null context");
+    FP_REQUIRE(B >= 0 && B <= 65535, "gt_visibility: B=%d instances (0..65535 per call)", B);
+    FP_REQUIRE(Hr > 0 && Wr > 0 && (size_t)Hr * Wr <= ((size_t)1 << 30), "gt_visibility: canvas %d x %d", Wr, Hr);
+    FP_REQUIRE(gi_window_ok(Wr, Hr, ox, oy, W, H), "gt_visibility: window %d x %d at (%d, %d) leaves the canvas %d x %d", W, H, ox, oy, Wr, Hr);
+    FP_REQUIRE(n_img > 0, "gt_visibility: n_img=%d test depth images (>= 1)", n_img);
+    if (B == 0) return FP_OK;
+    FP_REQUIRE(d_depth_gt && d_depth_test && d_img_idx && d_params && d_out, "gt_visibility: null d_depth_gt, d_depth_test, d_img_idx, d_params or d_out");
+    std::vector<int32_t> idx(B);
+    FP_HIP(hipMemcpyAsync(idx.data(), d_img_idx, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    FP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    for (int b = 0; b < B; ++b) FP_REQUIRE(gi_img_ok(idx[b], n_img), "gt_visibility: d_img_idx[%d] = %d outside [0, %d)", b, idx[b], n_img);
+    return fp_gt_visibility_launch(d_depth_gt, B, Hr, Wr, ox, oy, d_depth_test, n_img, H, W, d_img_idx, d_params, d_mask, d_mask_visib, d_out,
+                                   (hipStream_t)stream);
+}
+
+extern "C" int fp_pts_diameter(fp_ctx* ctx, const double* d_pts, int n_pts, const int32_t* d_ranges, int M, double* d_out, void* stream) {
+    FP_REQUIRE(ctx, "pts_diameter: null context");
+    FP_REQUIRE(M >= 0 && M <= 65535, "pts_diameter: M=%d models (0..65535 per call)", M);
+    FP_REQUIRE(n_pts >= 0, "pts_diameter: n_pts=%d", n_pts);
+    if (M == 0) return FP_OK;
+    FP_REQUIRE(d_pts && d_ranges && d_out, "pts_diameter: null d_pts, d_ranges or d_out");
+    std::vector<int32_t> rg((size_t)M * 2);
+    FP_HIP(hipMemcpyAsync(rg.data(), d_ranges, rg.size() * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    FP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    int max_count = 0;
+    for (int m = 0; m < M; ++m) {
+        FP_REQUIRE(gi_range_ok(rg[2 * m], rg[2 * m + 1], n_pts), "pts_diameter: range %d = {first %d, count %d} is empty or outside [0, %d]", m,
+                   rg[2 * m], rg[2 * m + 1], n_pts);
+        max_count = std::max(max_count, rg[2 * m + 1]);
+    }
+    FP_REQUIRE(max_count <= FP_DIAM_MAX_POINTS, "pts_diameter: a model of %d points (at most %d)", max_count, FP_DIAM_MAX_POINTS);
+    const size_t tiles = (size_t)cdiv(max_count, fp_pts_diameter_tile()), n_slots = (size_t)M * (tiles * (tiles + 1) / 2);
+    FP_REQUIRE(n_slots <= FP_DIAM_MAX_SLOTS, "pts_diameter: %d models of up to %d points need %zu per-block slots (at most %zu per call)", M,
+               max_count, n_slots, (size_t)FP_DIAM_MAX_SLOTS);
+    double* slots;
+    FP_WS(ctx, "diam.slots", n_slots * sizeof(double), slots);
+    return fp_pts_diameter_launch(d_pts, n_pts, d_ranges, M, max_count, slots, d_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

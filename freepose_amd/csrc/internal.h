@@ -122,3 +122,10 @@ int fp_video_errors_launch(const double* est, const double* gt, const int* meta,
 int fp_bop_scores_launch(const double* err, const int32_t* groups, const uint8_t* gt_valid, const int32_t* gt_obj, const int32_t* gt_scene,
                          const double* th, int P, int Gr, int R, int T, int n_obj, int n_scene, int n_top, int32_t* match, int32_t* tp_obj,
                          int32_t* tp_scene, int32_t* tar_obj, int32_t* tar_scene, hipStream_t s);
+// gt_info.hip: ground-truth visibility / masks / boxes per instance and model diameters (gt_info_core.h holds the host-checkable arithmetic)
+int fp_gt_visibility_launch(const float* d_gt, int B, int Hr, int Wr, int ox, int oy, const float* d_test, int n_img, int H, int W,
+                            const int* img_idx, const double* params, uint8_t* mask, uint8_t* mask_visib, int32_t* out, hipStream_t s);
+#define FP_DIAM_MAX_POINTS (1 << 21)          // points of one model (2048 tiles: 2.1 M tile pairs)
+#define FP_DIAM_MAX_SLOTS ((size_t)1 << 26)   // per-block maxima of one call (512 MiB of workspace)
+int fp_pts_diameter_tile(void);   // points per tile of fp_pts_diameter_launch; slots: M * n_pairs doubles, n_pairs = t (t + 1) / 2, t = tiles of max_count
+int fp_pts_diameter_launch(const double* pts, int n_pts, const int* ranges, int M, int max_count, double* slots, double* out, hipStream_t s);

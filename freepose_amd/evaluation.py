@@ -12,6 +12,10 @@ Numerics (DESIGN.md "Scoring"): cus / vsd are integer-exact given the same depth
 The second half turns those errors into scores: `BopScorer` packs the groups of an errors directory once and matches estimates to ground
 truths and counts recalls for all thresholds in one device call (fp_bop_scores; eval_calc_scores.py:188-290, pose_matching.py, score.py;
 DESIGN.md §16), exactly.
+
+The third part prepares the inputs of that chain: `GtInfoCalculator` computes the scene_gt_info records and the mask / mask_visib images
+of ground-truth instances (fp_gt_visibility over canvases of the HIP rasteriser; bop_toolkit/scripts/calc_gt_info.py, calc_gt_masks.py)
+and `models_info` the diameter and bounding box of models (fp_pts_diameter; calc_model_info.py, misc.calc_pts_diameter).
 """
 from __future__ import annotations
 
@@ -376,3 +380,124 @@ class BopScorer:
         res = ops.bop_scores(tables["err"], tables["groups"], tables["gt_valid"], tables["gt_obj"], tables["gt_scene"], thresholds,
                              len(self.obj_ids), len(self.scene_ids), int(n_top))
         return self.unpack(tables, thresholds, *[r.cpu().numpy() for r in res])
+
+
+# ---- ground-truth info: visibility, boxes, masks, model diameters (csrc/gt_info.hip) ----------------------------------------------------
+GT_INFO_KEYS = ("px_count_all", "px_count_valid", "px_count_visib", "visib_fract", "bbox_obj", "bbox_visib")    # calc_gt_info.py:176-185
+MODEL_INFO_KEYS = ("min_x", "min_y", "min_z", "size_x", "size_y", "size_z", "diameter")                         # calc_model_info.py:42-50
+RASTER_MAX_SIDE = 8192                 # the rasteriser's largest canvas side (csrc/raster.hip)
+# Canvas pixels rendered per batch.  The rasteriser holds 8 bytes of depth/id buffer per pixel in the context's workspace and the batch
+# holds its float32 depth and uint8 colour images next to it: 15 bytes per pixel, so one batch stays at or below 480 MiB (one canvas is
+# always rendered, whatever its size: 8192 x 8192 is 960 MiB).
+GT_INFO_CANVAS_PIXELS_PER_BATCH = 32 << 20
+
+
+def gt_info_from_counts(row) -> dict:
+    """one row of ops.gt_visibility -> the dict of calc_gt_info.py:154-185, keys in its order.  BOTH boxes are [-1, -1, -1, -1] when no
+    pixel is visible: the reference conditions bbox_obj on px_count_visib as well (:163)."""
+    r = [int(v) for v in row]
+    px_all, px_valid, px_visib = r[0], r[1], r[2]
+    visib_fract = px_visib / float(px_all) if px_all > 0 else 0.0
+    bbox, bbox_visib = [-1, -1, -1, -1], [-1, -1, -1, -1]
+    if px_visib > 0:
+        bbox = [r[4], r[5], r[6] - r[4], r[7] - r[5]]                    # misc.calc_2d_bbox: [x, y, max - min, max - min]
+        bbox_visib = [r[8], r[9], r[10] - r[8], r[11] - r[9]]
+    return {"px_count_all": px_all, "px_count_valid": px_valid, "px_count_visib": px_visib, "visib_fract": float(visib_fract),
+            "bbox_obj": bbox, "bbox_visib": bbox_visib}
+
+
+def model_info_from_row(row) -> dict:
+    """one row of ops.pts_diameter -> the dict of calc_model_info.py:42-50, keys in its order"""
+    r = [float(v) for v in row]
+    return {"min_x": r[1], "min_y": r[2], "min_z": r[3], "size_x": r[4], "size_y": r[5], "size_z": r[6], "diameter": r[0]}
+
+
+def models_info(clouds_by_obj: dict) -> dict:
+    """obj_id -> [N,3] float64 vertices  ->  obj_id -> model info, all models in one device call"""
+    ids = list(clouds_by_obj)
+    rows = ops.pts_diameter([clouds_by_obj[i] for i in ids]).cpu().numpy() if ids else []
+    return {i: model_info_from_row(r) for i, r in zip(ids, rows)}
+
+
+class GtInfoCalculator:
+    """scene_gt_info records and mask / mask_visib images of ground-truth instances (bop_toolkit/scripts/calc_gt_info.py, calc_gt_masks.py).
+
+    width, height: the dataset's image size.  An instance is (image key, obj_id, R [3,3], t [3]); depth_test_by_image maps the image key
+    to its depth image [height, width] in the unit of the models (float32, depth_scale applied), K_by_image to its 3x3 intrinsics.  The
+    instances of many images are rendered in batches of at most GT_INFO_CANVAS_PIXELS_PER_BATCH canvas pixels and handed to one fused
+    pass each (ops.gt_visibility)."""
+
+    def __init__(self, width: int, height: int, delta: float = 15):
+        self.width, self.height, self.delta = int(width), int(height), delta
+        if self.width < 1 or self.height < 1:
+            raise ValueError(f"image size {width} x {height}")
+        self._models = {}                           # obj_id -> [mesh, ops.Mesh | None]
+
+    def add_model(self, obj_id, mesh):
+        self._models[obj_id] = [mesh, None]
+        return self
+
+    def _device_model(self, obj_id):
+        if obj_id not in self._models:
+            raise KeyError(f"model {obj_id!r} was not registered (add_model)")
+        e = self._models[obj_id]
+        if e[1] is None:
+            e[1] = device_mesh(e[0])
+        return e[1]
+
+    def _run(self, instances, depth_test_by_image, K_by_image, large: bool, want_masks: bool):
+        W, H = self.width, self.height
+        Wr, Hr, ox, oy = (3 * W, 3 * H, W, H) if large else (W, H, 0, 0)
+        if Wr > RASTER_MAX_SIDE or Hr > RASTER_MAX_SIDE:
+            raise ValueError(f"image size {W} x {H}: the {Wr} x {Hr} canvas exceeds the rasteriser's {RASTER_MAX_SIDE} x {RASTER_MAX_SIDE}")
+        instances = list(instances)
+        n = len(instances)
+        rows = np.zeros((n, ops.GT_INFO_OUT_LD), np.int32)
+        masks = np.zeros((n, H, W), np.uint8) if want_masks else None
+        visibs = np.zeros((n, H, W), np.uint8) if want_masks else None
+        if n == 0:
+            return rows, masks, visibs
+        keys = []
+        for inst in instances:
+            if inst[0] not in keys:
+                keys.append(inst[0])
+        stack = []
+        for k in keys:
+            d = np.asarray(depth_test_by_image[k], np.float32)
+            if d.shape != (H, W):
+                raise ValueError(f"depth image of {k!r} is {d.shape[1]} x {d.shape[0]}, the dataset's image size is {W} x {H}")
+            stack.append(d)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_test = torch.from_numpy(np.stack(stack)).to(dev)
+        Ks = [np.asarray(K_by_image[inst[0]], np.float64).reshape(3, 3) for inst in instances]
+        idx = [keys.index(inst[0]) for inst in instances]
+        per_batch = max(1, GT_INFO_CANVAS_PIXELS_PER_BATCH // (Wr * Hr))
+        for b0 in range(0, n, per_batch):
+            b1 = min(n, b0 + per_batch)
+            canvas = torch.empty((b1 - b0, Hr, Wr), dtype=torch.float32, device=dev)
+            groups = OrderedDict()                  # one rasteriser call per (object, intrinsics)
+            for i in range(b0, b1):
+                K = Ks[i]
+                g = (instances[i][1], float(K[0, 0]), float(K[1, 1]), float(K[0, 2] + ox), float(K[1, 2] + oy))
+                groups.setdefault(g, []).append(i)
+            for (obj_id, fx, fy, cx, cy), members in groups.items():
+                P = torch.from_numpy(np.stack([_pose44(instances[i][2], instances[i][3]) for i in members]))
+                _, depth = ops.rasterize(self._device_model(obj_id), P, 1.0, fx, fy, cx, cy, Wr, Hr)
+                canvas[torch.as_tensor([i - b0 for i in members], device=dev)] = depth
+            c, m, v = ops.gt_visibility(canvas, d_test, idx[b0:b1], np.stack(Ks[b0:b1]), float(self.delta), window=(ox, oy),
+                                        want_masks=want_masks)
+            rows[b0:b1] = c.cpu().numpy()
+            if want_masks:
+                masks[b0:b1], visibs[b0:b1] = m.cpu().numpy(), v.cpu().numpy()
+        return rows, masks, visibs
+
+    def gt_info(self, instances, depth_test_by_image, K_by_image) -> list:
+        """one dict per instance, the reference's keys in its order (calc_gt_info.py:176-185); rendered on the 3W x 3H canvas with the
+        principal point shifted by (W, H), so that truncated silhouettes are counted (:70-74)"""
+        rows, _, _ = self._run(instances, depth_test_by_image, K_by_image, large=True, want_masks=False)
+        return [gt_info_from_counts(r) for r in rows]
+
+    def gt_masks(self, instances, depth_test_by_image, K_by_image):
+        """(mask u8 [n,H,W], mask_visib u8 [n,H,W]) on the host, 255 / 0 (calc_gt_masks.py:110-126); rendered at image size"""
+        _, masks, visibs = self._run(instances, depth_test_by_image, K_by_image, large=False, want_masks=True)
+        return masks, visibs

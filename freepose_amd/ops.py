@@ -844,6 +844,103 @@ def depth_compare(depth_est: torch.Tensor, depth_gt: torch.Tensor, depth_test: O
     return out
 
 
+# ---- ground-truth info (csrc/gt_info.hip) -----------------------------------------------------------
+GT_INFO_OUT_LD = 12                                        # csrc/gt_info_core.h FP_GI_OUT_LD
+GT_INFO_MAX_BATCH = 65535                                  # instances per launch (grid y); tests lower it
+GT_INFO_BOX_EMPTY = (2 ** 31 - 1, 2 ** 31 - 1, -2 ** 31, -2 ** 31)   # the box no pixel has touched
+DIAMETER_TILE = 1024                                       # csrc/gt_info.hip DM_TILE
+DIAMETER_MAX_POINTS = 1 << 21                              # csrc/internal.h FP_DIAM_MAX_POINTS
+DIAMETER_MAX_MODELS = 65535                                # models per launch (grid y); tests lower it
+DIAMETER_MAX_SLOTS = 1 << 24                               # per-block maxima per launch (128 MiB of workspace; the entry takes up to 2^26)
+
+
+def gt_visibility(depth_gt, depth_test, img_idx, K, delta, window=None, want_masks: bool = True):
+    """calc_gt_info.py:131-173 / calc_gt_masks.py:107-126 for B ground-truth instances in one fused pass each (fp_gt_visibility).
+    depth_gt f32 [B,Hr,Wr] rendered canvases; depth_test f32 [n_img,H,W] (or [H,W]) test depth in the unit of the renders; img_idx [B]
+    the image of each instance (None: image 0); K [3,3] | [B,3,3] the IMAGE's intrinsics; delta one value or [B]; window = (ox, oy): the
+    image is canvas[oy:oy+H, ox:ox+W] (None: the canvases have the image's size).
+    -> (counts i32 [B,12] = {px_count_all, px_count_valid, px_count_visib, 0, box of the silhouette: min x, min y, max x, max y relative to
+    the window, box of the visible mask}, mask u8 [B,H,W], mask_visib u8 [B,H,W]) on the device; the masks are None without want_masks.
+    An untouched box is GT_INFO_BOX_EMPTY.  ValueError for what the C entry would refuse."""
+    lib = _lib.load()
+    dg, dt = _dev(torch.as_tensor(depth_gt), torch.float32), _dev(torch.as_tensor(depth_test), torch.float32)
+    if dt.dim() == 2:
+        dt = dt[None]
+    if dg.dim() != 3 or dt.dim() != 3:
+        raise ValueError(f"gt_visibility: depth stacks {tuple(dg.shape)} and {tuple(dt.shape)} ([B,Hr,Wr] and [n_img,H,W])")
+    B, Hr, Wr = dg.shape
+    n_img, H, W = dt.shape
+    if window is None:
+        if (Hr, Wr) != (H, W):
+            raise ValueError(f"gt_visibility: canvases of {Wr} x {Hr} for images of {W} x {H} need a window")
+        ox, oy = 0, 0
+    else:
+        ox, oy = int(window[0]), int(window[1])
+    if n_img < 1 or H < 1 or W < 1 or Hr * Wr > 1 << 30:
+        raise ValueError(f"gt_visibility: {n_img} test images of {W} x {H}, canvas {Wr} x {Hr}")
+    if ox < 0 or oy < 0 or ox + W > Wr or oy + H > Hr:
+        raise ValueError(f"gt_visibility: window {W} x {H} at ({ox}, {oy}) leaves the canvas {Wr} x {Hr}")
+    idx = np.zeros(B, np.int32) if img_idx is None else np.asarray(img_idx, dtype=np.int64).reshape(-1)
+    if idx.size != B:
+        raise ValueError(f"gt_visibility: {idx.size} image indices for {B} instances")
+    if B and (idx.min() < 0 or idx.max() >= n_img):
+        raise ValueError(f"gt_visibility: img_idx outside [0, {n_img})")
+    Kb = _per_pair(K, B, (3, 3), "K")
+    prm = np.zeros((B, 8), dtype=np.float64)
+    prm[:, 0], prm[:, 1], prm[:, 2], prm[:, 3] = Kb[:, 0, 0], Kb[:, 1, 1], Kb[:, 0, 2], Kb[:, 1, 2]
+    prm[:, 4] = _per_pair(delta, B, (), "delta")
+    out = torch.empty((B, GT_INFO_OUT_LD), dtype=torch.int32, device=dg.device)
+    mask = torch.empty((B, H, W), dtype=torch.uint8, device=dg.device) if want_masks else None
+    visib = torch.empty((B, H, W), dtype=torch.uint8, device=dg.device) if want_masks else None
+    if B == 0:
+        return out, mask, visib
+    d_prm, d_idx = torch.from_numpy(prm).to(dg.device), torch.from_numpy(idx.astype(np.int32)).to(dg.device)
+    for b0 in range(0, B, GT_INFO_MAX_BATCH):
+        nb = min(GT_INFO_MAX_BATCH, B - b0)
+        check(lib.fp_gt_visibility(context(), ptr(dg[b0:]), nb, Hr, Wr, ox, oy, ptr(dt), n_img, H, W, ptr(d_idx[b0:]), ptr(d_prm[b0:]),
+                                   ptr(mask[b0:]) if want_masks else None, ptr(visib[b0:]) if want_masks else None, ptr(out[b0:]),
+                                   current_stream()), "fp_gt_visibility")
+    return out, mask, visib
+
+
+def pts_diameter(clouds) -> torch.Tensor:
+    """misc.calc_pts_diameter (misc.py:289-303) and the box of calc_model_info.py:36-37 for M vertex clouds at once (fp_pts_diameter).
+    clouds: list of [N_i,3] float64 arrays (numpy or tensors) -> f64 [M,8] on the device = {diameter, min x, y, z, size x, y, z, 0},
+    bit for bit the reference's float64 values.  Launches are split by model count and by the workspace of per-block maxima.
+    ValueError for an empty cloud or one above DIAMETER_MAX_POINTS points."""
+    lib = _lib.load()
+    cl = [_dev(torch.as_tensor(c), torch.float64).reshape(-1, 3) for c in clouds]
+    M = len(cl)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((M, 8), dtype=torch.float64, device=dev)
+    if M == 0:
+        return out
+    sizes = np.array([c.shape[0] for c in cl], dtype=np.int64)
+    if (sizes <= 0).any():
+        raise ValueError(f"pts_diameter: cloud {int(np.flatnonzero(sizes <= 0)[0])} is empty")
+    if sizes.max() > DIAMETER_MAX_POINTS:
+        raise ValueError(f"pts_diameter: a cloud of {int(sizes.max())} points (at most {DIAMETER_MAX_POINTS})")
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    if starts[-1] >= 1 << 31:
+        raise ValueError("pts_diameter: more than 2^31 points in one call")
+    pts = cl[0] if M == 1 else torch.cat(cl, dim=0)
+    tiles = -(-sizes // DIAMETER_TILE)
+    pairs = tiles * (tiles + 1) // 2
+    if pairs.max() > DIAMETER_MAX_SLOTS:
+        raise ValueError(f"pts_diameter: a cloud of {int(sizes.max())} points needs {int(pairs.max())} slots (limit {DIAMETER_MAX_SLOTS})")
+    m0 = 0
+    while m0 < M:                                          # a launch: at most DIAMETER_MAX_MODELS models, models x slots of the largest within the limit
+        m1, most = m0, 0
+        while m1 < M and m1 - m0 < DIAMETER_MAX_MODELS and (m1 == m0 or max(most, int(pairs[m1])) * (m1 - m0 + 1) <= DIAMETER_MAX_SLOTS):
+            most = max(most, int(pairs[m1]))
+            m1 += 1
+        rg = np.stack([starts[m0:m1], sizes[m0:m1]], axis=1).astype(np.int32)
+        d_rg = torch.from_numpy(rg).to(dev)
+        check(lib.fp_pts_diameter(context(), ptr(pts), int(starts[-1]), ptr(d_rg), m1 - m0, ptr(out[m0:]), current_stream()), "fp_pts_diameter")
+        m0 = m1
+    return out
+
+
 # ---- kernel-level ops (unit tests / microbenchmarks) ------------------------------------------------
 def gemm(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, epi: int = 0, gamma=None, resid=None,
          out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -478,6 +478,44 @@ int fp_bop_scores(fp_ctx* ctx, const double* d_err, const int32_t* d_groups, con
                   const int32_t* d_gt_scene, const double* d_th, int P, int Gr, int R, int T, int n_obj, int n_scene, int n_top,
                   int32_t* d_match, int32_t* d_tp_obj, int32_t* d_tp_scene, int32_t* d_tar_obj, int32_t* d_tar_scene, void* stream);
 
+/* ---- ground-truth info: visibility, boxes, masks per instance; diameter and box per model ------------------- */
+/* Replaces the per-instance work of bop_toolkit/scripts/calc_gt_info.py:125-173 and calc_gt_masks.py:107-126 (the toolkit renders with
+ * OpenGL and runs numpy over whole images per instance): one fused pass per instance over a rendered depth canvas
+ * d_depth_gt f32 [B,Hr,Wr] (fp_rasterize output) and the test depth image of its scene image, d_depth_test f32 [n_img,H,W] (in the unit
+ * of the renders) selected by d_img_idx i32 [B].  The image is the window [oy, oy+H) x [ox, ox+W) of the canvas: calc_gt_info.py renders
+ * on a 3W x 3H canvas with the principal point shifted by (W, H) (:70-74,116-128: Wr = 3W, Hr = 3H, ox = W, oy = H), calc_gt_masks.py at
+ * image size (Wr = W, Hr = H, ox = oy = 0).  d_params f64 [B,8] = {fx, fy, cx, cy, delta, 0, 0, 0} with the IMAGE's intrinsics.
+ * d_out i32 [B,12] per instance:
+ *   [0] px_count_all    canvas pixels with depth > 0 (:145)
+ *   [1] px_count_valid  window pixels with dist_gt > 0 and dist_test > 0 (:149)
+ *   [2] px_count_visib  window pixels of visibility.estimate_visib_mask_gt mode bop19 (visibility.py:34-38): distance images as
+ *                       misc.depth_im_to_dist_im_fast forms them in fp64 (misc.py:146-167), the float32 difference, delta in float32
+ *   [3] 0
+ *   [4..7]  min x, min y, max x, max y of the canvas pixels with depth > 0, minus (ox, oy): negative or beyond the image for a truncated
+ *           silhouette (:164-167);  [8..11] the same over the visible mask (:172-173).  An empty set leaves {INT32_MAX, INT32_MAX,
+ *           INT32_MIN, INT32_MIN}.
+ * d_mask u8 [B,H,W] | NULL: 255 where dist_gt > 0 in the window, else 0 (calc_gt_masks.py:110,121); d_mask_visib u8 [B,H,W] | NULL: 255
+ * on the visible mask (:113-126).  Every byte of both is written.
+ * Refused with FP_ERR_INVALID and a message before anything is launched: a window that leaves the canvas, null stacks, B < 0 or above
+ * 65535, n_img < 1, and a d_img_idx outside [0, n_img) (the B indices are copied to the host for this: the call synchronises the
+ * stream once).  B = 0 is legal and does nothing.  16-byte loads are used when Wr, W and ox are multiples of 4 and the stacks are
+ * 16-byte aligned, a scalar loop otherwise (same answers).  Integer atomics only: every value equals the reference's given the same
+ * depth images, and two calls give the same bits. */
+int fp_gt_visibility(fp_ctx* ctx, const float* d_depth_gt, int B, int Hr, int Wr, int ox, int oy, const float* d_depth_test, int n_img,
+                     int H, int W, const int32_t* d_img_idx, const double* d_params, uint8_t* d_mask, uint8_t* d_mask_visib,
+                     int32_t* d_out, void* stream);
+/* bop_toolkit_lib/misc.py:289-303 calc_pts_diameter (a Python loop over all point pairs) and the bounding box of
+ * scripts/calc_model_info.py:36-37 for M models in one call.  d_pts f64 [n_pts,3]: the vertex clouds back to back; d_ranges i32 [M,2] =
+ * {first row, count} per model; d_out f64 [M,8] = {diameter, min x, min y, min z, size x, size y, size z, 0}, size = max - min.
+ * Brute force over all pairs in fp64: per pair (dx dx + dy dy) + dz dz with d = p_i - p_j, added left to right without FMA — the value
+ * (pts_diff * pts_diff).sum(axis=1) holds — the maximum of the squares, then ONE correctly rounded square root (sqrt is monotone: this
+ * is the reference's maximum of square roots).  Tile pairs i-tile <= j-tile, per-block maxima in workspace slots, a final kernel
+ * reduces them; no floating-point atomics: bit-exact, and two calls give the same bits.
+ * Refused before anything is launched: null tables, M < 0 or above 65535, a range with count = 0 or outside [0, n_pts] (the ranges are
+ * copied to the host for this: one stream synchronisation), a model above 2^21 points, more than 2^26 per-block slots in one call
+ * (M x t (t + 1) / 2, t = ceil(largest count / 1024)).  M = 0 is legal and does nothing. */
+int fp_pts_diameter(fp_ctx* ctx, const double* d_pts, int n_pts, const int32_t* d_ranges, int M, double* d_out, void* stream);
+
 /* ---- measurement helpers (bench.py: HIP-event timing on the launch stream) ----------------------------- */
 int fp_timer_create(void** out);
 int fp_timer_start(void* timer, void* stream);
