@@ -18,13 +18,27 @@
 // One workgroup = 4 waves x 16 queries of one (crop, head).  Key tiles of 64 are staged through registers (the global loads of tile
 // t+1 are in flight under the products of tile t) into one LDS image: K row-major, V transposed by the staging writes.  Online softmax
 // over the key tiles with the running maximum raised every tile: any sequence length.
+//
+// CAUSAL = true is the attention of open_clip's text transformer, whose mask hides every key after the query:
+//
+//   O[b, t, h*hd + d] = sum_{j <= t} softmax_j( q[b,t,h] . k[b,j,h] * scale ) v[b,j,h,d]        over the real tokens j <= t
+//
+// Layout, contract, staging and both products are the ones above.  What differs:
+//   * the workgroup of queries [q0, q0 + 64) walks the key tiles 0 .. floor(min(q0 + 63, n_tok - 1) / 64) only (attn_hd_core.h
+//     fp_ahd_causal_num_tiles): tiles wholly above the diagonal are skipped, not masked — at 77 tokens the first query block does one
+//     tile instead of two;
+//   * inside a visited tile a logit with key > query is replaced like a pad key (fp_ahd_causal_visible), before the maximum, so its P is
+//     exactly 0.  The rows of such FUTURE keys are real data and are loaded; V rows enter the second product multiplied by P = 0, which
+//     is exact for finite values, and whatever the first product made of a future K row (infinities and NaNs included) is discarded by
+//     the select.
+// Pad query rows see every real key and produce finite values under either mask.
 #include "internal.h"
 #include "attn_hd_core.h"
 
 namespace {
 
 constexpr int KT = FP_AHD_KEY_TILE;   // keys per tile
-constexpr int QBLK = 64;              // queries per workgroup (4 waves x 16)
+constexpr int QBLK = FP_AHD_QUERY_BLOCK;   // queries per workgroup (4 waves x 16)
 constexpr int VPITCH = FP_AHD_V_PITCH;   // bytes per V^T row in LDS (64 keys + one 16-byte slot: rows start on different banks)
 
 struct AttnHdArgs {
@@ -34,7 +48,7 @@ struct AttnHdArgs {
     float scale_log2e;              // scale * log2(e)
 };
 
-template <int NKK>   // padded head dimension = 32 * NKK
+template <int NKK, bool CAUSAL>   // padded head dimension = 32 * NKK; CAUSAL: query t attends to keys 0 .. t
 __global__ __launch_bounds__(256) void attn_hd_kernel(AttnHdArgs p) {
     constexpr int HDP = 32 * NKK;
     constexpr int NCH = fp_ahd_chunks(NKK);  // 16-byte chunks per padded row
@@ -49,7 +63,9 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(AttnHdArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
     const int h = blockIdx.y, b = blockIdx.z;
-    const int q0 = blockIdx.x * QBLK + wave * 16;
+    const int qblk = blockIdx.x * QBLK;
+    const int q0 = qblk + wave * 16;
+    const int qc = CAUSAL ? q0 + li : 0;   // this lane's query for the causal mask (the other flavour needs it only to load and to store)
     const bool idle = q0 >= p.npad;        // no row to store: the wave only takes part in staging and barriers
     const size_t rowbase = (size_t)b * p.npad;
     const bf16_t* gq = p.QKV + (size_t)h * p.hd;
@@ -69,7 +85,7 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(AttnHdArgs p) {
         }
     }
 
-    // ---- staging: global -> registers -> LDS -----------------------------------------------------------------------------------
+    // ---- staging: global -> registers -> LDS (pad rows are zero-filled; future rows of a visited tile are real and are loaded) ---
     uint4 rk[KI], rv0[VI], rv1[VI];
     auto load_tile = [&](int kv0) {
 #pragma unroll
@@ -117,7 +133,8 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(AttnHdArgs p) {
     float mrow = -1e30f;   // running maximum of the query's logits (log2 units), the same on the query's four lanes
     float lsum = 0.f;      // this lane's share of the running sum of P
 
-    const int ntile = fp_ahd_num_tiles(p.n_tok);
+    // the same count on every wave of the workgroup (causal: it depends on the block's first query only): the barriers below stay uniform
+    const int ntile = CAUSAL ? fp_ahd_causal_num_tiles(qblk, p.n_tok) : fp_ahd_num_tiles(p.n_tok);
     load_tile(0);
     for (int t = 0; t < ntile; ++t) {
         const int kv0 = t * KT;
@@ -145,12 +162,16 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(AttnHdArgs p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int key = kv0 + fp_ahd_acc_key(fk, lg, r);
-                s[fk][r] = fp_ahd_row_real(key, p.n_tok) ? s[fk][r] * p.scale_log2e : -1e30f;   // pad keys are masked
+                const bool seen = CAUSAL ? fp_ahd_causal_visible(key, qc, p.n_tok) : fp_ahd_row_real(key, p.n_tok);
+                s[fk][r] = seen ? s[fk][r] * p.scale_log2e : -1e30f;   // pad keys (causal: and future keys) are masked
                 mx = fmaxf(mx, s[fk][r]);
             }
         mx = fmaxf(mx, lane_xor<16>(mx));
         mx = fmaxf(mx, lane_xor<32>(mx));
-        const float mnew = fmaxf(mrow, mx);           // finite: every tile holds at least one real key
+        // finite from the first tile on: key 0 is real (n_tok >= 1), lies in tile 0 and is visible to every query (0 <= q), so tile 0
+        // gives every lane a finite mx.  A later tile of the causal walk may hold no visible key for a query (mx = -1e30): mnew stays
+        // the finite mrow, alpha = 1, and every P of that tile is exp2(-1e30 - mnew) = 0
+        const float mnew = fmaxf(mrow, mx);
         const float alpha = __builtin_amdgcn_exp2f(mrow - mnew);   // first tile: exp2(-1e30) = 0 on accumulators that are 0
         mrow = mnew;
         lsum *= alpha;
@@ -205,29 +226,41 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(AttnHdArgs p) {
     }
 }
 
-}  // namespace
-
-// QKV [B*npad, 3*heads*head_dim] (ldqkv elements), O [B*npad, heads*head_dim] (ldo elements); scale multiplies q.k before the softmax
-int fp_attention_hd_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
-                        hipStream_t stream) {
-    FP_REQUIRE(QKV && O, "attention_hd: null argument");
-    FP_REQUIRE(fp_ahd_head_dim_ok(head_dim), "attention_hd: head_dim=%d (must be a multiple of 8 in [8, 128])", head_dim);
-    FP_REQUIRE(B > 0 && heads > 0 && n_tok > 0 && npad >= n_tok && npad % 16 == 0, "attention_hd: bad shape B=%d heads=%d n_tok=%d npad=%d (npad %% 16 == 0, n_tok <= npad)",
-               B, heads, n_tok, npad);
+// the checks and the launch of both entries; who: "attention_hd" / "attention_causal", the first word of every refusal
+template <bool CAUSAL>
+int launch(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale, hipStream_t stream,
+           const char* who) {
+    FP_REQUIRE(QKV && O, "%s: null argument", who);
+    FP_REQUIRE(fp_ahd_head_dim_ok(head_dim), "%s: head_dim=%d (must be a multiple of 8 in [8, 128])", who, head_dim);
+    FP_REQUIRE(B > 0 && heads > 0 && n_tok > 0 && npad >= n_tok && npad % 16 == 0, "%s: bad shape B=%d heads=%d n_tok=%d npad=%d (npad %% 16 == 0, n_tok <= npad)",
+               who, B, heads, n_tok, npad);
     FP_REQUIRE(ldqkv % 8 == 0 && ldo % 8 == 0 && ldqkv >= 3 * heads * head_dim && ldo >= heads * head_dim,
-               "attention_hd: leading dimensions ldqkv=%d ldo=%d (multiples of 8, at least 3 * width / width)", ldqkv, ldo);
-    FP_REQUIRE(heads <= 65535 && B <= 65535, "attention_hd: heads=%d B=%d exceed the grid", heads, B);
+               "%s: leading dimensions ldqkv=%d ldo=%d (multiples of 8, at least 3 * width / width)", who, ldqkv, ldo);
+    FP_REQUIRE(heads <= 65535 && B <= 65535, "%s: heads=%d B=%d exceed the grid", who, heads, B);
     AttnHdArgs a;
     a.QKV = QKV; a.ldqkv = ldqkv; a.O = O; a.ldo = ldo;
     a.heads = heads; a.hd = head_dim; a.n_tok = n_tok; a.npad = npad;
     a.scale_log2e = scale * 1.4426950408889634f;
     const dim3 grid(cdiv(npad, QBLK), heads, B);
     switch (fp_ahd_k_steps(head_dim)) {
-        case 1: hipLaunchKernelGGL(attn_hd_kernel<1>, grid, dim3(256), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL(attn_hd_kernel<2>, grid, dim3(256), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL(attn_hd_kernel<3>, grid, dim3(256), 0, stream, a); break;
-        default: hipLaunchKernelGGL(attn_hd_kernel<4>, grid, dim3(256), 0, stream, a); break;
+        case 1: hipLaunchKernelGGL((attn_hd_kernel<1, CAUSAL>), grid, dim3(256), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((attn_hd_kernel<2, CAUSAL>), grid, dim3(256), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((attn_hd_kernel<3, CAUSAL>), grid, dim3(256), 0, stream, a); break;
+        default: hipLaunchKernelGGL((attn_hd_kernel<4, CAUSAL>), grid, dim3(256), 0, stream, a); break;
     }
     FP_LAUNCH_CHECK();
     return FP_OK;
+}
+
+}  // namespace
+
+// QKV [B*npad, 3*heads*head_dim] (ldqkv elements), O [B*npad, heads*head_dim] (ldo elements); scale multiplies q.k before the softmax
+int fp_attention_hd_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
+                        hipStream_t stream) {
+    return launch<false>(QKV, ldqkv, O, ldo, B, heads, head_dim, n_tok, npad, scale, stream, "attention_hd");
+}
+// the same under the causal mask: query t attends to keys 0 .. t
+int fp_attention_causal_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
+                            hipStream_t stream) {
+    return launch<true>(QKV, ldqkv, O, ldo, B, heads, head_dim, n_tok, npad, scale, stream, "attention_causal");
 }

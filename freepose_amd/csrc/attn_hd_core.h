@@ -1,4 +1,4 @@
-// Index arithmetic of attention_hd.hip, attention_causal.hip and of the k-nearest-rows selection (retrieval.hip), kept free of device
+// Index arithmetic of attention_hd.hip (both masks) and of the k-nearest-rows selection (retrieval.hip), kept free of device
 // intrinsics so that a host program can run it under the sanitizers (tools/attn_hd_host_check.cpp, tools/attn_causal_host_check.cpp):
 // supported shapes, the pad masks, the key-tile tail, the staging and fragment offsets into the LDS images,
 // the row permutation that lines the first product's accumulators up with the second product's operand, the tile walk and visibility
@@ -51,7 +51,7 @@ FP_HD int fp_ahd_vstage_off(int c, int w) { return (fp_ahd_vstage_d0(c) + w) * F
 FP_HD int fp_ahd_kfrag_off(int fk, int li, int lg, int kk, int kpitch) { return fp_ahd_tile_key(fk, li) * kpitch + lg * 16 + kk * 64; }
 FP_HD int fp_ahd_vfrag_off(int fd, int li, int lg, int ks) { return (16 * fd + li) * FP_AHD_V_PITCH + lg * 16 + ks * 64; }
 
-// ---- causal attention (attention_causal.hip): query t sees keys 0 .. t.  A workgroup owns FP_AHD_QUERY_BLOCK consecutive queries and
+// ---- causal attention (attention_hd.hip, CAUSAL = true): query t sees keys 0 .. t.  A workgroup owns FP_AHD_QUERY_BLOCK consecutive queries and
 // walks the key tiles from 0 up to the one that holds the last key any of its queries sees; tiles wholly above the diagonal are never
 // staged.  Pad queries (rows [n_tok, npad)) see every real key.
 #define FP_AHD_QUERY_BLOCK 64

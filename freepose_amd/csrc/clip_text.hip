@@ -9,11 +9,7 @@
 //   pooled[b] = ln_final(x[b, argmax_t ids[b,t]])  ->  @ text_projection                             (first maximum)
 //
 // ln_final works per row, so normalising only the pooled row equals open_clip's "normalise every row, then index".  Built from the pieces
-// of the image tower (tower_steps.h, the bf16 GEMM tiers, the LayerNorm kernel) plus attention_causal.hip and the two gathers below.
-#include <stdio.h>
-
-#include <cmath>
-
+// of the image tower (tower_steps.h, the bf16 GEMM tiers, the LayerNorm kernel) plus the causal flavour of attention_hd.hip and the two gathers below.
 #include "../../include/freepose_hip.h"
 #include "tower_steps.h"
 
@@ -61,58 +57,37 @@ __global__ __launch_bounds__(256) void text_pool_kernel(const int* __restrict__ 
     for (int c = threadIdx.x; c < D / 8; c += blockDim.x) dst[c] = src[c];
 }
 
-// dst [cols, rows] = src [rows, cols]^T (text_projection is stored [width, embed_dim] and applied as x @ P; the GEMM wants [out, in])
-__global__ void text_transpose_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int rows, int cols) {
-    const size_t total = (size_t)rows * cols;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t c = i / rows, r = i - c * rows;
-        dst[i] = src[r * cols + c];
-    }
-}
-
 }  // namespace
 
 struct fp_clip_text {
     fp_ctx* ctx = nullptr;
     fp_clip_text_arch a{};
-    int head_dim = 0, npad = 0;
+    int npad = 0;
     const bf16_t *tok = nullptr, *pos = nullptr, *lnfw = nullptr, *lnfb = nullptr;
-    bf16_t* projT = nullptr;      // [embed_dim, width] private transposed copy of text_projection
-    bf16_t* ones = nullptr;       // gamma of the residual epilogue (no LayerScale in CLIP)
-    bf16_t* zeros = nullptr;      // bias of the projection GEMM (the layer has none)
     int* bad = nullptr;           // raised by the embedding gather on an id outside the vocabulary
-    bool have_proj = false;
-    std::vector<TowerBlockW> blk;
+    ClipTowerCommon tw;           // text_projection transposed, ones / zeros, the blocks
 };
 
 extern "C" int fp_clip_text_create(fp_ctx* ctx, const fp_clip_text_arch* arch, fp_clip_text** out) {
     FP_REQUIRE(ctx && arch && out, "clip_text_create: null argument");
-    FP_REQUIRE(arch->width > 0 && arch->width % 64 == 0 && arch->heads > 0 && arch->width % arch->heads == 0,
-               "clip_text_create: width=%d heads=%d (width must be a multiple of 64 and of heads)", arch->width, arch->heads);
-    const int hd = arch->width / arch->heads;
-    FP_REQUIRE(hd % 8 == 0 && hd >= 8 && hd <= 128, "clip_text_create: head dimension %d (must be a multiple of 8 in [8, 128])", hd);
-    FP_REQUIRE(arch->width <= 2048, "clip_text_create: width=%d exceeds the LayerNorm kernel (2048)", arch->width);
-    FP_REQUIRE(arch->mlp_dim > 0 && arch->mlp_dim % 64 == 0 && arch->embed_dim > 0 && arch->embed_dim % 16 == 0 && arch->depth > 0 &&
-                   arch->vocab > 0 && arch->ctx > 0, "clip_text_create: bad arch (mlp_dim %% 64, embed_dim %% 16, depth, vocab, ctx)");
+    if (int rc = ClipTowerCommon::check_arch("clip_text_create", arch->width, arch->heads, arch->mlp_dim, arch->embed_dim, arch->depth,
+                                             arch->vocab > 0 && arch->ctx > 0, "vocab, ctx")) return rc;
     fp_clip_text* v = new fp_clip_text();
     v->ctx = ctx;
     v->a = *arch;
-    v->head_dim = hd;
     v->npad = cdiv(arch->ctx, 16) * 16;
-    v->blk.resize(arch->depth);
-    const size_t W = arch->width, E = arch->embed_dim, nvec = std::max(W, E);
-    if (hipMalloc((void**)&v->projT, E * W * 2) != hipSuccess || hipMalloc((void**)&v->ones, nvec * 2) != hipSuccess ||
-        hipMalloc((void**)&v->zeros, nvec * 2) != hipSuccess || hipMalloc((void**)&v->bad, sizeof(int)) != hipSuccess) {
+    int rc = v->tw.alloc("clip_text_create", arch->width, arch->heads, arch->embed_dim, arch->depth);
+    if (!rc && hipMalloc((void**)&v->bad, sizeof(int)) != hipSuccess) {
         fp_set_error("clip_text_create: hipMalloc failed");
-        fp_clip_text_destroy(v);
-        return FP_ERR_HIP;
+        rc = FP_ERR_HIP;
     }
-    std::vector<bf16_t> one(nvec, f2bf(1.0f));
-    if (hipMemset(v->zeros, 0, nvec * 2) != hipSuccess || hipMemset(v->bad, 0, sizeof(int)) != hipSuccess ||
-        hipMemcpy(v->ones, one.data(), nvec * 2, hipMemcpyHostToDevice) != hipSuccess) {
+    if (!rc && hipMemset(v->bad, 0, sizeof(int)) != hipSuccess) {
         fp_set_error("clip_text_create: initialising the device buffers failed");
+        rc = FP_ERR_HIP;
+    }
+    if (rc) {
         fp_clip_text_destroy(v);
-        return FP_ERR_HIP;
+        return rc;
     }
     *out = v;
     return FP_OK;
@@ -120,10 +95,8 @@ extern "C" int fp_clip_text_create(fp_ctx* ctx, const fp_clip_text_arch* arch, f
 
 extern "C" int fp_clip_text_destroy(fp_clip_text* v) {
     if (!v) return FP_OK;
-    if (v->projT) (void)hipFree(v->projT);
-    if (v->ones) (void)hipFree(v->ones);
-    if (v->zeros) (void)hipFree(v->zeros);
     if (v->bad) (void)hipFree(v->bad);
+    v->tw.free();
     delete v;
     return FP_OK;
 }
@@ -133,30 +106,12 @@ extern "C" int fp_clip_text_set_weight(fp_clip_text* v, const char* name, const 
     const fp_clip_text_arch& a = v->a;
     const bf16_t* p = (const bf16_t*)d;
     const size_t D = a.width, M = a.mlp_dim, E = a.embed_dim;
-    hipStream_t s = (hipStream_t)stream;
-    if (!strcmp(name, "text_projection")) {
-        if (!fp_weight_numel("clip_text_set_weight", name, numel, D * E)) return FP_ERR_INVALID;
-        hipLaunchKernelGGL(text_transpose_kernel, dim3((unsigned)std::min<size_t>((D * E + 255) / 256, 4096)), dim3(256), 0, s, p, v->projT, (int)D, (int)E);
-        FP_LAUNCH_CHECK();
-        v->have_proj = true;
-        return FP_OK;
-    }
+    if (!strcmp(name, "text_projection")) return v->tw.set_proj("clip_text_set_weight", name, p, numel, D, E, (hipStream_t)stream);
     const WeightEnt top[] = {{"token_embedding.weight", &v->tok, (size_t)a.vocab * D}, {"positional_embedding", &v->pos, (size_t)a.ctx * D},
                              {"ln_final.weight", &v->lnfw, D}, {"ln_final.bias", &v->lnfb, D}};
-    if (const int hit = fp_set_named_weight("clip_text_set_weight", name, name, top, p, numel)) return hit > 0 ? FP_OK : FP_ERR_INVALID;
-    int bi = -1;
-    char rest[64] = {0};
-    if (sscanf(name, "transformer.resblocks.%d.%63s", &bi, rest) == 2 && bi >= 0 && bi < a.depth) {
-        TowerBlockW& w = v->blk[bi];
-        const WeightEnt tab[] = {
-            {"ln_1.weight", &w.n1w, D}, {"ln_1.bias", &w.n1b, D},
-            {"attn.in_proj_weight", &w.qkvw, 3 * D * D}, {"attn.in_proj_bias", &w.qkvb, 3 * D},
-            {"attn.out_proj.weight", &w.projw, D * D}, {"attn.out_proj.bias", &w.projb, D},
-            {"ln_2.weight", &w.n2w, D}, {"ln_2.bias", &w.n2b, D},
-            {"mlp.c_fc.weight", &w.fc1w, M * D}, {"mlp.c_fc.bias", &w.fc1b, M},
-            {"mlp.c_proj.weight", &w.fc2w, D * M}, {"mlp.c_proj.bias", &w.fc2b, D}};
-        if (const int hit = fp_set_named_weight("clip_text_set_weight", name, rest, tab, p, numel)) return hit > 0 ? FP_OK : FP_ERR_INVALID;
-    }
+    int hit = fp_set_named_weight("clip_text_set_weight", name, name, top, p, numel);
+    if (!hit) hit = fp_tower_resblock_weight("clip_text_set_weight", name, v->tw.blk, D, M, p, numel);
+    if (hit) return hit > 0 ? FP_OK : FP_ERR_INVALID;
     fp_set_error("clip_text_set_weight: unknown tensor name '%s'", name);
     return FP_ERR_INVALID;
 }
@@ -166,17 +121,14 @@ extern "C" int fp_clip_text_encode(fp_clip_text* v, const int32_t* d_ids, int B,
     const fp_clip_text_arch& a = v->a;
     hipStream_t s = (hipStream_t)stream;
     FP_REQUIRE(B > 0, "clip_text_encode: B=%d", B);
-    FP_REQUIRE(v->have_proj && v->tok && v->pos && v->lnfw && v->lnfb, "clip_text_encode: embedding / ln_final / text_projection weights not set");
-    for (int i = 0; i < a.depth; ++i) {
-        FP_REQUIRE(v->blk[i].complete(), "clip_text_encode: weights of block %d not set", i);
-    }
+    FP_REQUIRE(v->tw.have_proj && v->tok && v->pos && v->lnfw && v->lnfb, "clip_text_encode: embedding / ln_final / text_projection weights not set");
+    int rc;
+    if ((rc = v->tw.all_blocks_complete("clip_text_encode"))) return rc;
     const int D = a.width, n_tok = a.ctx, npad = v->npad;
     const size_t M = (size_t)B * npad;
-    FP_REQUIRE(M * (size_t)std::max(a.mlp_dim, 3 * D) * 2 < 0xffffffffull, "clip_text_encode: batch too large for 32-bit tile offsets (B=%d)", B);
-    const int Mi = (int)M;
+    if ((rc = fp_tower_offsets_fit("clip_text_encode", M, D, a.mlp_dim, B))) return rc;
 
     bf16_t *X, *Y, *QKV, *AO, *H1, *POOL, *POOLN;
-    int rc;
     fp_ctx* ctx = v->ctx;
     FP_WS(ctx, "clip_text.x", M * D * 2, X);
     FP_WS(ctx, "clip_text.y", M * D * 2, Y);
@@ -203,21 +155,13 @@ extern "C" int fp_clip_text_encode(fp_clip_text* v, const int32_t* d_ids, int B,
     }
     bf16_t* R = X;    // residual stream
     bf16_t* T = Y;    // LayerNorm output of the current half block
-    const TowerRun t{ctx, nullptr, s, B, n_tok, npad, D, a.mlp_dim, a.ln_eps, R, T, AO, H1, v->ones};
-    const float scale = 1.0f / sqrtf((float)v->head_dim);
-    for (int i = 0; i < a.depth; ++i) {
-        const TowerBlockW& w = v->blk[i];
-        if ((rc = fp_layernorm(R, T, w.n1w, w.n1b, Mi, D, a.ln_eps, 0, 0, 0, s))) return rc;
-        if ((rc = GemmStep(T, D, w.qkvw, D, QKV, 3 * D, w.qkvb, Mi, 3 * D).run(ctx, s))) return rc;
-        if ((rc = fp_attention_causal_fwd(QKV, 3 * D, AO, D, B, a.heads, v->head_dim, n_tok, npad, scale, s))) return rc;
-        if ((rc = fp_tower_out_proj(t, w, nullptr))) return rc;
-        if ((rc = fp_tower_mlp(t, w, nullptr, nullptr, nullptr, nullptr))) return rc;
-    }
+    const TowerRun t{ctx, nullptr, s, B, n_tok, npad, D, a.mlp_dim, a.ln_eps, R, T, AO, H1, v->tw.ones};
+    if ((rc = fp_tower_blocks(t, v->tw.blk, QKV, a.heads, v->tw.head_dim, /*causal=*/true))) return rc;
     // ---- the end-of-text row of every prompt, ln_final, then the projection ---------------------------------------------------------------
     hipLaunchKernelGGL(text_pool_kernel, dim3(B), dim3(256), 0, s, d_ids, R, POOL, n_tok, npad, D);
     FP_LAUNCH_CHECK();
     if ((rc = fp_layernorm(POOL, POOLN, v->lnfw, v->lnfb, B, D, a.ln_eps, 0, 0, 0, s))) return rc;
-    return GemmStep(POOLN, D, v->projT, D, (bf16_t*)d_out, a.embed_dim, v->zeros, B, a.embed_dim).run(ctx, s);
+    return v->tw.project(ctx, POOLN, D, a.embed_dim, d_out, B, s);
 }
 
 extern "C" double fp_clip_text_flops(const fp_clip_text* v, int B) {

@@ -52,7 +52,7 @@ int fp_attention_fwd(const bf16_t* QK, int ldqk, const bf16_t* Vt, bf16_t* O, in
 // attention_hd.hip: any head dimension (multiple of 8 up to 128) on the plain [q | k | v] output of one bias GEMM
 int fp_attention_hd_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
                         hipStream_t stream);
-// attention_causal.hip: the same layout and contract, query t attending to keys 0 .. t (the CLIP text tower)
+// the same kernel, layout and contract, query t attending to keys 0 .. t (the CLIP text tower)
 int fp_attention_causal_fwd(const bf16_t* QKV, int ldqkv, bf16_t* O, int ldo, int B, int heads, int head_dim, int n_tok, int npad, float scale,
                             hipStream_t stream);
 // vit_misc.hip
@@ -67,6 +67,7 @@ int fp_posembed_aa(const bf16_t* src, bf16_t* dst, int G, int gh, int gw, int D,
 int fp_ffa_pool(const bf16_t* feats, const uint8_t* mask, bf16_t* out, float* out_f32, int B, int P, int D, int gh,
                 int gw, int cell, uint8_t* pm_scratch, hipStream_t s, bf16_t* out_norm = nullptr, int* arrive = nullptr);
 int fp_l2norm_rows(const bf16_t* X, bf16_t* Y, int rows, int D, hipStream_t s);
+int fp_transpose_bf16(const bf16_t* src, bf16_t* dst, int rows, int cols, hipStream_t s);   // dst [cols, rows] = src [rows, cols]^T
 // LayerNorm folded into the consuming GEMM (gemm_bf16.h FP_EPI_LN_*): row statistics and the one-off weight fold
 int fp_row_stats(const bf16_t* X, uint4* mfrag, float* rstd, int rows, int D, float eps, hipStream_t s);
 int fp_stats_finalize(const float2* part, uint4* mfrag, float* rstd, int rows, int D, float eps, hipStream_t s, int part_ld = 0);   // part_ld: row stride of part (0 = rows)

@@ -1,8 +1,12 @@
-// The steps the transformer drivers (vit.hip, clip.hip) and the kernel-level test entries (capi.hip) are built from: GEMM launches
-// by the name of the layer form, the LayerNorm-statistics hand-off between a producing and a consuming GEMM, the per-class timing of a
-// tower, and the parts of a forward the DINOv2 and CLIP towers have in common.  Host code only; every launch goes through fp_ctx::gemm.
+// The steps the transformer drivers (vit.hip, clip.hip, clip_text.hip) and the kernel-level test entries (capi.hip) are built from: GEMM
+// launches by the name of the layer form, the LayerNorm-statistics hand-off between a producing and a consuming GEMM, the per-class timing
+// of a tower, the parts of a forward the DINOv2 and CLIP towers have in common, and the resblock tower the two CLIP towers are.
+// Host code only; every launch goes through fp_ctx::gemm.
 #pragma once
+#include <stdio.h>
 #include <string.h>
+
+#include <cmath>
 
 #include "internal.h"
 
@@ -181,5 +185,97 @@ inline int fp_tower_set_patch_weight(const char* who, const char* name, const bf
     const size_t K = (size_t)3 * e.patch * e.patch;
     if (!fp_weight_numel(who, name, numel, D * K)) return FP_ERR_INVALID;
     FP_HIP(hipMemcpy2DAsync(e.pe_w, (size_t)e.KP * 2, p, K * 2, K * 2, D, hipMemcpyDeviceToDevice, s));
+    return FP_OK;
+}
+
+// ---- the CLIP towers (clip.hip, clip_text.hip): open_clip's resblocks, which the image and the text transformer share ---------------
+// "transformer.resblocks.<i>.<rest>" of a tower of width D and MLP width M: fp_set_named_weight's answer (0 also for any other name)
+inline int fp_tower_resblock_weight(const char* who, const char* name, std::vector<TowerBlockW>& blk, size_t D, size_t M, const bf16_t* p, size_t numel) {
+    int bi = -1;
+    char rest[64] = {0};
+    if (sscanf(name, "transformer.resblocks.%d.%63s", &bi, rest) != 2 || bi < 0 || bi >= (int)blk.size()) return 0;
+    TowerBlockW& w = blk[bi];
+    const WeightEnt tab[] = {
+        {"ln_1.weight", &w.n1w, D}, {"ln_1.bias", &w.n1b, D},
+        {"attn.in_proj_weight", &w.qkvw, 3 * D * D}, {"attn.in_proj_bias", &w.qkvb, 3 * D},
+        {"attn.out_proj.weight", &w.projw, D * D}, {"attn.out_proj.bias", &w.projb, D},
+        {"ln_2.weight", &w.n2w, D}, {"ln_2.bias", &w.n2b, D},
+        {"mlp.c_fc.weight", &w.fc1w, M * D}, {"mlp.c_fc.bias", &w.fc1b, M},
+        {"mlp.c_proj.weight", &w.fc2w, D * M}, {"mlp.c_proj.bias", &w.fc2b, D}};
+    return fp_set_named_weight(who, name, rest, tab, p, numel);
+}
+// depth x { R += out_proj(attn(ln_1 R)) ; R += c_proj(gelu(c_fc(ln_2 R))) } on the plain [q | k | v] rows QKV [M, 3 D]
+inline int fp_tower_blocks(const TowerRun& t, const std::vector<TowerBlockW>& blk, bf16_t* QKV, int heads, int head_dim, bool causal) {
+    const int D = t.D, M = t.M();
+    const float scale = 1.0f / sqrtf((float)head_dim);
+    int rc;
+    for (const TowerBlockW& w : blk) {
+        if ((rc = fp_layernorm(t.R, t.T, w.n1w, w.n1b, M, D, t.eps, 0, 0, 0, t.s))) return rc;
+        if ((rc = GemmStep(t.T, D, w.qkvw, D, QKV, 3 * D, w.qkvb, M, 3 * D).run(t.ctx, t.s))) return rc;
+        if ((rc = (causal ? fp_attention_causal_fwd : fp_attention_hd_fwd)(QKV, 3 * D, t.AO, D, t.B, heads, head_dim, t.n_tok, t.npad, scale, t.s))) return rc;
+        if ((rc = fp_tower_out_proj(t, w, nullptr))) return rc;
+        if ((rc = fp_tower_mlp(t, w, nullptr, nullptr, nullptr, nullptr))) return rc;
+    }
+    return FP_OK;
+}
+// what both towers own besides their embeddings.  who: the entry's name, the first word of its refusals
+struct ClipTowerCommon {
+    int head_dim = 0;
+    bf16_t* projT = nullptr;      // [embed_dim, width] private transposed copy of the projection
+    bf16_t* ones = nullptr;       // gamma of the residual epilogue (no LayerScale in CLIP)
+    bf16_t* zeros = nullptr;      // bias of the GEMMs whose layer has none (the projection; the image tower's patch embedding)
+    bool have_proj = false;
+    std::vector<TowerBlockW> blk;
+    // rest_ok / rest_names: the fields only one of the towers has
+    static int check_arch(const char* who, int width, int heads, int mlp_dim, int embed_dim, int depth, bool rest_ok, const char* rest_names) {
+        FP_REQUIRE(width > 0 && width % 64 == 0 && heads > 0 && width % heads == 0, "%s: width=%d heads=%d (width must be a multiple of 64 and of heads)",
+                   who, width, heads);
+        const int hd = width / heads;
+        FP_REQUIRE(hd % 8 == 0 && hd >= 8 && hd <= 128, "%s: head dimension %d (must be a multiple of 8 in [8, 128])", who, hd);
+        FP_REQUIRE(width <= 2048, "%s: width=%d exceeds the LayerNorm kernel (2048)", who, width);
+        FP_REQUIRE(mlp_dim > 0 && mlp_dim % 64 == 0 && embed_dim > 0 && embed_dim % 16 == 0 && depth > 0 && rest_ok,
+                   "%s: bad arch (mlp_dim %% 64, embed_dim %% 16, depth, %s)", who, rest_names);
+        return FP_OK;
+    }
+    int alloc(const char* who, int width, int heads, int embed_dim, int depth) {
+        head_dim = width / heads;
+        blk.resize(depth);
+        const size_t W = width, E = embed_dim, nvec = std::max(W, E);
+        if (hipMalloc((void**)&projT, E * W * 2) != hipSuccess || hipMalloc((void**)&ones, nvec * 2) != hipSuccess ||
+            hipMalloc((void**)&zeros, nvec * 2) != hipSuccess) {
+            fp_set_error("%s: hipMalloc failed", who);
+            return FP_ERR_HIP;
+        }
+        std::vector<bf16_t> one(nvec, f2bf(1.0f));
+        if (hipMemset(zeros, 0, nvec * 2) != hipSuccess || hipMemcpy(ones, one.data(), nvec * 2, hipMemcpyHostToDevice) != hipSuccess) {
+            fp_set_error("%s: initialising the device buffers failed", who);
+            return FP_ERR_HIP;
+        }
+        return FP_OK;
+    }
+    void free() {
+        if (projT) (void)hipFree(projT);
+        if (ones) (void)hipFree(ones);
+        if (zeros) (void)hipFree(zeros);
+    }
+    // p: the [D, E] projection as open_clip stores it (applied as x @ p; the GEMM wants [out, in])
+    int set_proj(const char* who, const char* name, const bf16_t* p, size_t numel, size_t D, size_t E, hipStream_t s) {
+        if (!fp_weight_numel(who, name, numel, D * E)) return FP_ERR_INVALID;
+        if (int rc = fp_transpose_bf16(p, projT, (int)D, (int)E, s)) return rc;
+        have_proj = true;
+        return FP_OK;
+    }
+    int all_blocks_complete(const char* who) const {
+        for (size_t i = 0; i < blk.size(); ++i) FP_REQUIRE(blk[i].complete(), "%s: weights of block %d not set", who, (int)i);
+        return FP_OK;
+    }
+    // out [B, E] = pooled [B, D] @ projection
+    int project(fp_ctx* ctx, const bf16_t* pooled, int D, int E, void* out, int B, hipStream_t s) const {
+        return GemmStep(pooled, D, projT, D, (bf16_t*)out, E, zeros, B, E).run(ctx, s);
+    }
+};
+// the GEMM tiers address a launch's tiles with 32-bit byte offsets: M rows of the widest activation (fc1's or qkv's output) must fit
+inline int fp_tower_offsets_fit(const char* who, size_t M, int D, int mlp_dim, int B) {
+    FP_REQUIRE(M * (size_t)std::max(mlp_dim, 3 * D) * 2 < 0xffffffffull, "%s: batch too large for 32-bit tile offsets (B=%d)", who, B);
     return FP_OK;
 }

@@ -5,6 +5,7 @@
 //                   dino.py:23-30)
 //   posembed_aa   : bicubic antialias resize of the 37x37 pos-embed grid (hub DINOv2
 //                   interpolate_pos_encoding; public algorithm of torch upsample_bicubic2d_aa)
+//   transpose     : [rows, cols] -> [cols, rows] (the CLIP projections, once per weight load)
 //   ffa           : mask any-pool 14x14 -> masked mean over patches -> optional L2 normalise
 //                   (scripts/extract_retrieval_features.py:51-57, extract_proposals_ground.py:129-134)
 #include "internal.h"
@@ -335,6 +336,16 @@ __global__ __launch_bounds__(256) void l2norm_rows_vec_kernel(const bf16_t* X, b
     d64_norm_store<NCH>(a, d64_row_norm(wave_sum(acc)), Y + (size_t)r * D, D, lane);
 }
 
+// dst [cols, rows] = src [rows, cols]^T (the CLIP projections are stored [width, embed_dim] and applied as x @ proj; the GEMM wants
+// [out, in]).  Once per weight load
+__global__ void transpose_bf16_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int rows, int cols) {
+    const size_t total = (size_t)rows * cols;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t c = i / rows, r = i - c * rows;
+        dst[i] = src[r * cols + c];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // LayerNorm folded into the consuming GEMM (gemm_bf16.h FP_EPI_LN_*): what is left of LN1 / LN2 are per-row statistics.
 // Both kernels write, per row, the init-MFMA operand record of gemm_bf16.h — {sh, sl, sh, -mh, -ml, -mh, 0, 0}: sigma = sqrt(var + eps)
@@ -518,6 +529,13 @@ int fp_ffa_pool(const bf16_t* feats, const uint8_t* mask, bf16_t* out, float* ou
     }
     FP_REQUIRE(!arrive || (out && out_norm && D % 8 == 0), "ffa: the fused normalisation needs both bf16 buffers and D %% 8 == 0");
     hipLaunchKernelGGL(ffa_kernel, dim3(cdiv(D, 64), B), dim3(1024), P, s, feats, pm, out, out_f32, P, D, out_norm, arrive);
+    FP_LAUNCH_CHECK();
+    return FP_OK;
+}
+
+int fp_transpose_bf16(const bf16_t* src, bf16_t* dst, int rows, int cols, hipStream_t s) {
+    const size_t total = (size_t)rows * cols;
+    hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, src, dst, rows, cols);
     FP_LAUNCH_CHECK();
     return FP_OK;
 }

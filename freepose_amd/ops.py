@@ -1029,48 +1029,38 @@ def attention(qk: torch.Tensor, vt: torch.Tensor, n_tok: int, out: Optional[torc
     return out
 
 
+def _attention_qkv(entry_name: str, qkv: torch.Tensor, heads: int, n_tok: int, scale: Optional[float], out: Optional[torch.Tensor]) -> torch.Tensor:
+    """attention_hd / attention_causal: the C entry fp_op_<entry_name> on the [q | k | v] rows"""
+    lib = _lib.load()
+    qkv = _dev(qkv, torch.bfloat16)
+    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads) != 0:
+        raise ValueError(f"{entry_name}: qkv of shape {tuple(qkv.shape)} ([B, npad, 3*heads*hd]) with heads={heads}")
+    B, npad, w3 = qkv.shape
+    width = w3 // 3
+    hd = width // heads
+    if out is None:
+        out = torch.zeros((B, npad, width), dtype=torch.bfloat16, device=qkv.device)
+    else:
+        assert out.dtype == torch.bfloat16 and out.is_cuda and tuple(out.shape) == (B, npad, width)
+        assert out.stride(2) == 1 and out.stride(0) == npad * out.stride(1)
+    sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(hd))
+    entry = "fp_op_" + entry_name
+    check(getattr(lib, entry)(ptr(qkv), w3, ptr(out), int(out.stride(1)), B, heads, hd, int(n_tok), npad, sc, current_stream()), entry)
+    return out
+
+
 def attention_hd(qkv: torch.Tensor, heads: int, n_tok: int, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """attention for any head dimension (a multiple of 8 up to 128) on the plain output of one bias GEMM (fp_op_attention_hd):
     qkv bf16 [B, npad, 3*heads*hd], columns [q | k | v] (nn.MultiheadAttention's in_proj order) -> o bf16 [B, npad, heads*hd], the
     softmax running over the first n_tok tokens of each crop.  scale defaults to 1/sqrt(hd).  `out`: optional bf16 [B, npad, width]
     whose rows are contiguous B*npad and whose row stride may exceed the width (a column slice of a wider buffer)."""
-    lib = _lib.load()
-    qkv = _dev(qkv, torch.bfloat16)
-    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads) != 0:
-        raise ValueError(f"attention_hd: qkv of shape {tuple(qkv.shape)} ([B, npad, 3*heads*hd]) with heads={heads}")
-    B, npad, w3 = qkv.shape
-    width = w3 // 3
-    hd = width // heads
-    if out is None:
-        out = torch.zeros((B, npad, width), dtype=torch.bfloat16, device=qkv.device)
-    else:
-        assert out.dtype == torch.bfloat16 and out.is_cuda and tuple(out.shape) == (B, npad, width)
-        assert out.stride(2) == 1 and out.stride(0) == npad * out.stride(1)
-    sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(hd))
-    check(lib.fp_op_attention_hd(ptr(qkv), w3, ptr(out), int(out.stride(1)), B, heads, hd, int(n_tok), npad, sc, current_stream()),
-          "fp_op_attention_hd")
-    return out
+    return _attention_qkv("attention_hd", qkv, heads, n_tok, scale, out)
 
 
 def attention_causal(qkv: torch.Tensor, heads: int, n_tok: int, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """attention_hd under a causal mask (fp_op_attention_causal, the attention of the CLIP text tower): the same arguments and layout;
     token t attends to the tokens 0 .. t of its prompt."""
-    lib = _lib.load()
-    qkv = _dev(qkv, torch.bfloat16)
-    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads) != 0:
-        raise ValueError(f"attention_causal: qkv of shape {tuple(qkv.shape)} ([B, npad, 3*heads*hd]) with heads={heads}")
-    B, npad, w3 = qkv.shape
-    width = w3 // 3
-    hd = width // heads
-    if out is None:
-        out = torch.zeros((B, npad, width), dtype=torch.bfloat16, device=qkv.device)
-    else:
-        assert out.dtype == torch.bfloat16 and out.is_cuda and tuple(out.shape) == (B, npad, width)
-        assert out.stride(2) == 1 and out.stride(0) == npad * out.stride(1)
-    sc = float(scale) if scale is not None else 1.0 / float(np.sqrt(hd))
-    check(lib.fp_op_attention_causal(ptr(qkv), w3, ptr(out), int(out.stride(1)), B, heads, hd, int(n_tok), npad, sc, current_stream()),
-          "fp_op_attention_causal")
-    return out
+    return _attention_qkv("attention_causal", qkv, heads, n_tok, scale, out)
 
 
 def knn_l2(table: torch.Tensor, queries: torch.Tensor, k: int):
@@ -1103,17 +1093,49 @@ CLIP_ARCHS = {
 }
 
 
-def clip_state_dict_names(model_name: str) -> dict:
-    """open_clip visual state-dict name -> shape"""
-    width, depth, heads, mlp, embed, patch, grid = CLIP_ARCHS[model_name]
-    names = {"conv1.weight": (width, 3, patch, patch), "class_embedding": (width,), "positional_embedding": (1 + grid * grid, width),
-             "ln_pre.weight": (width,), "ln_pre.bias": (width,), "ln_post.weight": (width,), "ln_post.bias": (width,), "proj": (width, embed)}
+def _resblock_names(width: int, mlp: int, depth: int) -> dict:
+    """open_clip's transformer.resblocks.<i>.* name -> shape, block by block (both towers; the order is the one the seeded random
+    state dicts draw in)"""
+    names = {}
     for i in range(depth):
         p = f"transformer.resblocks.{i}."
         names.update({p + "ln_1.weight": (width,), p + "ln_1.bias": (width,), p + "attn.in_proj_weight": (3 * width, width),
                       p + "attn.in_proj_bias": (3 * width,), p + "attn.out_proj.weight": (width, width), p + "attn.out_proj.bias": (width,),
                       p + "ln_2.weight": (width,), p + "ln_2.bias": (width,), p + "mlp.c_fc.weight": (mlp, width), p + "mlp.c_fc.bias": (mlp,),
                       p + "mlp.c_proj.weight": (width, mlp), p + "mlp.c_proj.bias": (width,)})
+    return names
+
+
+class _ClipTower:
+    """what ClipVisual and ClipText share: registering a state dict with the library and releasing the handle.  A subclass names its
+    tower (_WHAT, in the error text), its name table (_names) and its C entries (_SET_WEIGHT, _DESTROY)"""
+
+    def load_state_dict(self, sd: dict):
+        s = current_stream()
+        want = self._names(self.model_name)
+        missing = sorted(set(want) - set(sd))
+        if missing:
+            raise KeyError(f"{self._WHAT} state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
+        set_weight = getattr(self.lib, self._SET_WEIGHT)
+        for name in want:
+            w = _dev(torch.as_tensor(sd[name]), torch.bfloat16)
+            self.weights[name] = w  # keep alive: the library stores raw pointers
+            check(set_weight(self.handle, name.encode(), ptr(w), w.numel(), s), f"set_weight({name})")
+        torch.cuda.synchronize()
+
+    def __del__(self):
+        try:
+            getattr(self.lib, self._DESTROY)(self.handle)
+        except Exception:
+            pass
+
+
+def clip_state_dict_names(model_name: str) -> dict:
+    """open_clip visual state-dict name -> shape"""
+    width, depth, heads, mlp, embed, patch, grid = CLIP_ARCHS[model_name]
+    names = {"conv1.weight": (width, 3, patch, patch), "class_embedding": (width,), "positional_embedding": (1 + grid * grid, width),
+             "ln_pre.weight": (width,), "ln_pre.bias": (width,), "ln_post.weight": (width,), "ln_post.bias": (width,), "proj": (width, embed)}
+    names.update(_resblock_names(width, mlp, depth))
     return names
 
 
@@ -1137,8 +1159,9 @@ def random_clip_state_dict(model_name: str, seed: int = 0) -> dict:
     return {k: v.to(torch.bfloat16) for k, v in sd.items()}
 
 
-class ClipVisual:
+class ClipVisual(_ClipTower):
     """Device-resident CLIP image tower (open_clip visual state-dict layout) driving fp_clip_encode_image."""
+    _WHAT, _names, _SET_WEIGHT, _DESTROY = "CLIP", staticmethod(clip_state_dict_names), "fp_clip_set_weight", "fp_clip_destroy"
 
     def __init__(self, model_name: str = "ViT-bigG-14", state_dict: Optional[dict] = None, seed: int = 0, device: Optional[int] = None,
                  quick_gelu: bool = False):
@@ -1156,18 +1179,6 @@ class ClipVisual:
         self.weights = {}
         self.load_state_dict(state_dict if state_dict is not None else random_clip_state_dict(model_name, seed))
 
-    def load_state_dict(self, sd: dict):
-        s = current_stream()
-        want = clip_state_dict_names(self.model_name)
-        missing = sorted(set(want) - set(sd))
-        if missing:
-            raise KeyError(f"CLIP state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        for name in want:
-            w = _dev(torch.as_tensor(sd[name]), torch.bfloat16)
-            self.weights[name] = w  # keep alive: the library stores raw pointers
-            check(self.lib.fp_clip_set_weight(self.handle, name.encode(), ptr(w), w.numel(), s), f"set_weight({name})")
-        torch.cuda.synchronize()
-
     def encode_image(self, images: torch.Tensor) -> torch.Tensor:
         """bf16 [B,3,S,S] in [0,1] -> bf16 [B, embed_dim]"""
         x = _dev(images, torch.bfloat16)
@@ -1183,12 +1194,6 @@ class ClipVisual:
 
     def flops(self, B: int) -> float:
         return float(self.lib.fp_clip_flops(self.handle, int(B)))
-
-    def __del__(self):
-        try:
-            self.lib.fp_clip_destroy(self.handle)
-        except Exception:
-            pass
 
 
 # ---- CLIP text tower (csrc/clip_text.hip) -------------------------------------------------------------
@@ -1213,12 +1218,7 @@ def clip_text_state_dict_names(model_name: str) -> dict:
     width, depth, heads, mlp, vocab, ctx, embed = CLIP_TEXT_ARCHS[model_name]
     names = {"token_embedding.weight": (vocab, width), "positional_embedding": (ctx, width), "ln_final.weight": (width,),
              "ln_final.bias": (width,), "text_projection": (width, embed)}
-    for i in range(depth):
-        p = f"transformer.resblocks.{i}."
-        names.update({p + "ln_1.weight": (width,), p + "ln_1.bias": (width,), p + "attn.in_proj_weight": (3 * width, width),
-                      p + "attn.in_proj_bias": (3 * width,), p + "attn.out_proj.weight": (width, width), p + "attn.out_proj.bias": (width,),
-                      p + "ln_2.weight": (width,), p + "ln_2.bias": (width,), p + "mlp.c_fc.weight": (mlp, width), p + "mlp.c_fc.bias": (mlp,),
-                      p + "mlp.c_proj.weight": (width, mlp), p + "mlp.c_proj.bias": (width,)})
+    names.update(_resblock_names(width, mlp, depth))
     return names
 
 
@@ -1244,8 +1244,9 @@ def random_clip_text_state_dict(model_name: str, seed: int = 0) -> dict:
     return {k: v.to(torch.bfloat16) for k, v in sd.items()}
 
 
-class ClipText:
+class ClipText(_ClipTower):
     """Device-resident CLIP text tower (open_clip state-dict names) driving fp_clip_text_encode."""
+    _WHAT, _names, _SET_WEIGHT, _DESTROY = "CLIP text", staticmethod(clip_text_state_dict_names), "fp_clip_text_set_weight", "fp_clip_text_destroy"
 
     def __init__(self, model_name: str = "ViT-bigG-14", state_dict: Optional[dict] = None, seed: int = 0, device: Optional[int] = None,
                  chunk: int = 256):
@@ -1262,18 +1263,6 @@ class ClipText:
         self.handle = h
         self.weights = {}
         self.load_state_dict(state_dict if state_dict is not None else random_clip_text_state_dict(model_name, seed))
-
-    def load_state_dict(self, sd: dict):
-        s = current_stream()
-        want = clip_text_state_dict_names(self.model_name)
-        missing = sorted(set(want) - set(sd))
-        if missing:
-            raise KeyError(f"CLIP text state dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
-        for name in want:
-            w = _dev(torch.as_tensor(sd[name]), torch.bfloat16)
-            self.weights[name] = w  # keep alive: the library stores raw pointers
-            check(self.lib.fp_clip_text_set_weight(self.handle, name.encode(), ptr(w), w.numel(), s), f"set_weight({name})")
-        torch.cuda.synchronize()
 
     def encode_text(self, ids: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
         """token ids [N, ctx] (any integer dtype) -> bf16 [N, embed_dim], `chunk` prompts per tower call (bounded workspaces; a prompt's
@@ -1293,12 +1282,6 @@ class ClipText:
 
     def flops(self, B: int) -> float:
         return float(self.lib.fp_clip_text_flops(self.handle, int(B)))
-
-    def __del__(self):
-        try:
-            self.lib.fp_clip_text_destroy(self.handle)
-        except Exception:
-            pass
 
 
 def im2col_norm(images: torch.Tensor, ps: int = 14, kp: Optional[int] = None) -> torch.Tensor:

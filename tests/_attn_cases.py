@@ -1,4 +1,4 @@
-"""Structured inputs for the three attention kernels (csrc/attention.hip, attention_hd.hip, attention_causal.hip) whose correct output
+"""Structured inputs for the three attention kernels (csrc/attention.hip, attention_hd.hip and its causal flavour) whose correct output
 is known exactly or to one bf16 neighbour, the float64 references, and a Python mirror of each kernel's dispatch.  Imports without a GPU;
 tests/test_attn_cases_cpu.py proves the claims made here, tests/test_gpu_attention_exact.py runs the kernels on the cases.
 
@@ -118,7 +118,7 @@ def bf16_neighbour(got, ref, atol=0.0):
 
 KV_TILE = 64            # keys per tile, all three kernels
 DINO_QB, DINO_QW = 128, 32   # attention.hip: queries per workgroup / per wave (two 16-query halves)
-HD_QB, HD_QW = 64, 16        # attention_hd.hip, attention_causal.hip
+HD_QB, HD_QW = 64, 16        # attention_hd.hip, either mask
 THR2 = 40.0 * 1.4426950408889634 / 8.0   # attention.hip, pre-scaled path: the lazy threshold in log2 units
 THR_NAT = 5.0                            # attention.hip, plain path: LAZY_THR = 40 logits = 5 nats
 

@@ -167,21 +167,24 @@ def _kernel_notes(obj: Path, tmp_path):
 
 
 def test_new_kernels_have_no_scratch(tmp_path):
-    """the four causal instantiations (padded head dimension 32 / 64 / 96 / 128) and the text tower's gathers compile to zero scratch and
-    no spills, read from the code objects' metadata notes; attention_hd.o still holds exactly its own four kernels"""
+    """the eight instantiations of the general-head attention kernel (padded head dimension 32 / 64 / 96 / 128, causal and not), the
+    text tower's gathers and the projection transpose compile to zero scratch and no spills, read from the code objects' metadata
+    notes; attention_hd.o holds exactly those eight"""
     from freepose_amd import build
     build.build_hip(verbose=False)
     obj = ROOT / "freepose_amd" / "lib" / "obj"
-    causal = {k: v for k, v in _kernel_notes(obj / "attention_causal.o", tmp_path).items() if "attn_causal_kernel" in k}
-    assert len(causal) == 4, sorted(causal)
+    attn = {k: v for k, v in _kernel_notes(obj / "attention_hd.o", tmp_path).items() if "attn_hd_kernel" in k}
+    assert len(attn) == 8, sorted(attn)
+    assert len([k for k in attn if "Lb1" in k]) == 4 and len([k for k in attn if "Lb0" in k]) == 4, sorted(attn)   # CAUSAL = true / false
     text = _kernel_notes(obj / "clip_text.o", tmp_path)
-    gathers = {k: v for k, v in text.items() if "text_embed_kernel" in k or "text_pool_kernel" in k or "text_transpose_kernel" in k}
-    assert len(gathers) == 3, sorted(text)
-    for k, v in {**causal, **gathers}.items():
+    gathers = {k: v for k, v in text.items() if "text_embed_kernel" in k or "text_pool_kernel" in k}
+    assert len(gathers) == 2, sorted(text)
+    misc = _kernel_notes(obj / "vit_misc.o", tmp_path)
+    transpose = {k: v for k, v in misc.items() if "transpose_bf16_kernel" in k}
+    assert len(transpose) == 1, sorted(misc)
+    for k, v in {**attn, **gathers, **transpose}.items():
         print(k, v)
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["vgpr_count"] <= 256, (k, v)
-    hd = _kernel_notes(obj / "attention_hd.o", tmp_path)
-    assert len([k for k in hd if "attn_hd_kernel" in k]) == 4 and not [k for k in hd if "causal" in k]
 
 
 def test_causal_index_arithmetic_under_the_host_sanitizers(tmp_path):
@@ -195,11 +198,12 @@ def test_causal_index_arithmetic_under_the_host_sanitizers(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0 and "attn_causal_host_check: ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    src = (ROOT / "freepose_amd" / "csrc" / "attention_causal.hip").read_text()
+    csrc = ROOT / "freepose_amd" / "csrc"
+    src = (csrc / "attention_hd.hip").read_text()
     for fn in ("fp_ahd_causal_num_tiles", "fp_ahd_causal_visible", "fp_ahd_kstage_off", "fp_ahd_vstage_off", "fp_ahd_kfrag_off", "fp_ahd_vfrag_off",
                "fp_ahd_acc_key", "fp_ahd_row_real", "fp_ahd_chunk_real"):
         assert fn + "(" in src, fn
-    assert "attn_hd_kernel" not in src
+    assert not (csrc / "attention_causal.hip").exists()
 
 
 # ---- fail closed ----------------------------------------------------------------------------------------------------------------------------

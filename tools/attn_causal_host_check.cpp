@@ -1,4 +1,4 @@
-// Host check of the index rules attention_causal.hip adds to those of attention_hd.hip (csrc/attn_hd_core.h: fp_ahd_causal_num_tiles,
+// Host check of the index rules the causal flavour of attention_hd.hip adds to the others (csrc/attn_hd_core.h: fp_ahd_causal_num_tiles,
 // fp_ahd_causal_visible), meant to be built with the host sanitizers:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ifreepose_amd/csrc tools/attn_causal_host_check.cpp -o attn_causal_host_check
 // For a sweep of sequence lengths it replays, per query block, which key tiles the workgroup walks and which logits it keeps, against

@@ -7,7 +7,8 @@ tests/golden/gpt4_scale_names.json; only the text tower is built.  Prints
   * one 256-prompt encode_text call (HIP events on the launch stream, 3 warm-up calls, median (minimum) of 10) and its split: the causal
     attention and LayerNorm kernels ALONE on tensors of the call's shapes, per launch, times their launch count; the remainder is
     "GEMM + gathers";
-  * the causal kernel next to fp_op_attention_hd on the same [B, 80, 3 * width] buffer (77 real tokens)."""
+  * the causal flavour of csrc/attention_hd.hip next to the unmasked one (fp_op_attention_hd) on the same [B, 80, 3 * width] buffer
+    (77 real tokens)."""
 from __future__ import annotations
 
 import argparse
