@@ -8,6 +8,7 @@
 #include "pnp_core.h"
 #include "video_eval_core.h"
 #include "gt_info_core.h"
+#include "lk_core.h"
 
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -634,4 +635,38 @@ extern "C" int fp_timer_destroy(void* t) {
     (void)hipEventDestroy(((FpTimer*)t)->b);
     delete (FpTimer*)t;
     return FP_OK;
+}
+
+// ---- the built-in point tracker (lk_track.hip) ------------------------------------------------------------------------------------------
+#define FP_LK_MAX_QUERIES (1 << 20)
+static int lk_check_sizes(const char* what, int T, int H, int W, int levels, int radius) {
+    FP_REQUIRE(T >= 1 && T <= 65535, "%s: T=%d frames (1..65535)", what, T);
+    FP_REQUIRE(H >= 1 && W >= 1 && H <= FP_LK_MAX_SIDE && W <= FP_LK_MAX_SIDE, "%s: %d x %d frames (1..%d per side)", what, H, W, FP_LK_MAX_SIDE);
+    FP_REQUIRE((long long)T * H * W <= (1ll << 30), "%s: T * H * W = %lld pixels (at most 2^30 per call)", what, (long long)T * H * W);
+    FP_REQUIRE(radius >= 1 && radius <= FP_LK_MAX_RADIUS, "%s: radius=%d (1..%d)", what, radius, FP_LK_MAX_RADIUS);
+    FP_REQUIRE(levels >= 1 && levels <= FP_LK_MAX_LEVELS, "%s: levels=%d (1..%d)", what, levels, FP_LK_MAX_LEVELS);
+    return FP_OK;
+}
+
+extern "C" int fp_lk_pyramid(fp_ctx* ctx, const uint8_t* d_frames, int T, int H, int W, int levels, int radius, float* d_pyramid, void* stream) {
+    FP_REQUIRE(ctx && d_frames && d_pyramid, "lk_pyramid: null argument");
+    if (int rc = lk_check_sizes("lk_pyramid", T, H, W, levels, radius)) return rc;
+    LkPyramid P;
+    lk_pyramid_layout(T, H, W, levels, radius, P);
+    return fp_lk_pyramid_launch(d_frames, P, d_pyramid, (hipStream_t)stream);
+}
+
+extern "C" int fp_lk_track(fp_ctx* ctx, const float* d_pyramid, int T, int H, int W, int levels, const float* d_queries, int N, int radius,
+                           int iters, float fb_thresh, float min_eig, float max_residual, float* d_tracks, uint8_t* d_vis, float* d_diag,
+                           void* stream) {
+    if (int rc = lk_check_sizes("lk_track", T, H, W, levels, radius)) return rc;
+    FP_REQUIRE(N >= 0 && N <= FP_LK_MAX_QUERIES, "lk_track: N=%d queries (0..2^20)", N);
+    FP_REQUIRE(ctx && d_pyramid && (N == 0 || (d_queries && d_tracks && d_vis && d_diag)), "lk_track: null argument");
+    FP_REQUIRE(iters >= 1 && iters <= FP_LK_MAX_ITERS, "lk_track: iters=%d (1..%d)", iters, FP_LK_MAX_ITERS);
+    LkPyramid P;
+    lk_pyramid_layout(T, H, W, levels, radius, P);
+    double* state = nullptr;                       // chain positions in fp64 (the float32 tracks are their rounded copies)
+    if (N > 0) FP_WS(ctx, "lk_state", (size_t)T * N * 2 * sizeof(double), state);
+    return fp_lk_track_launch(P, d_pyramid, d_queries, N, radius, iters, fb_thresh, min_eig, max_residual, state, d_tracks, d_vis, d_diag,
+                              (hipStream_t)stream);
 }

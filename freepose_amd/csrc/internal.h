@@ -130,3 +130,8 @@ int fp_gt_visibility_launch(const float* d_gt, int B, int Hr, int Wr, int ox, in
 #define FP_DIAM_MAX_SLOTS ((size_t)1 << 26)   // per-block maxima of one call (512 MiB of workspace)
 int fp_pts_diameter_tile(void);   // points per tile of fp_pts_diameter_launch; slots: M * n_pairs doubles, n_pairs = t (t + 1) / 2, t = tiles of max_count
 int fp_pts_diameter_launch(const double* pts, int n_pts, const int* ranges, int M, int max_count, double* slots, double* out, hipStream_t s);
+// lk_track.hip: the built-in pyramidal Lucas-Kanade point tracker (lk_core.h holds the host-checkable arithmetic and the pyramid layout)
+struct LkPyramid;
+int fp_lk_pyramid_launch(const uint8_t* frames, const LkPyramid& P, float* pyr, hipStream_t s);
+int fp_lk_track_launch(const LkPyramid& P, const float* pyr, const float* queries, int N, int radius, int iters, float fb_thresh,
+                       float min_eig, float max_residual, double* state, float* tracks, uint8_t* vis, float* diag, hipStream_t s);   // state: T * N * 2 doubles

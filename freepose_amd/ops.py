@@ -549,6 +549,73 @@ def pnp_epnp(pts3d, pts2d, K, vis=None) -> torch.Tensor:
     return out
 
 
+# ---- the built-in point tracker: pyramidal Lucas-Kanade (csrc/lk_track.hip) -------------------------
+LK_MAX_LEVELS, LK_MAX_RADIUS, LK_MAX_ITERS = 8, 15, 64     # csrc/lk_core.h
+LK_FLAG_FB, LK_FLAG_EIG, LK_FLAG_RESIDUAL, LK_FLAG_OUTSIDE, LK_FLAG_LOST_BEFORE = 1, 2, 4, 8, 16
+
+
+def lk_layout(H: int, W: int, levels: int, radius: int):
+    """[(h_l, w_l)] of the levels fp_lk_pyramid keeps (csrc/lk_core.h lk_pyramid_layout): h_l = (h_{l-1} + 1) // 2, a level whose smaller
+    side is below 2 radius + 1 is dropped with all coarser ones, level 0 always stays"""
+    sizes = [(int(H), int(W))]
+    for _ in range(1, int(levels)):
+        h, w = (sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2
+        if min(h, w) < 2 * int(radius) + 1:
+            break
+        sizes.append((h, w))
+    return sizes
+
+
+def lk_pyramid(frames, levels: int = 4, radius: int = 7) -> torch.Tensor:
+    """frames u8 [T,H,W,3] (RGB) -> the grey pyramid as one f32 device tensor, the levels of lk_layout back to back, each [T,h_l,w_l]
+    (fp_lk_pyramid; split it with lk_levels)"""
+    lib = _lib.load()
+    f = _dev(torch.as_tensor(frames))
+    if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3:
+        raise ValueError(f"lk_pyramid: frames {f.dtype} {tuple(f.shape)} (uint8 [T,H,W,3])")
+    T, H, W = (int(v) for v in f.shape[:3])
+    n = sum(T * h * w for h, w in lk_layout(H, W, levels, radius)) if 1 <= int(levels) <= LK_MAX_LEVELS and 1 <= int(radius) <= LK_MAX_RADIUS else 1
+    out = torch.empty(max(n, 1), dtype=torch.float32, device=f.device)
+    check(lib.fp_lk_pyramid(context(), ptr(f) if f.numel() else None, T, H, W, int(levels), int(radius), ptr(out), current_stream()),
+          "fp_lk_pyramid")
+    return out
+
+
+def lk_levels(pyramid: torch.Tensor, T: int, H: int, W: int, levels: int, radius: int):
+    """views [T,h_l,w_l] of the levels of an lk_pyramid tensor"""
+    out, off = [], 0
+    for h, w in lk_layout(H, W, levels, radius):
+        out.append(pyramid[off:off + T * h * w].view(T, h, w))
+        off += T * h * w
+    return out
+
+
+def lk_track(pyramid: torch.Tensor, T: int, H: int, W: int, queries, levels: int = 4, radius: int = 7, iters: int = 10,
+             fb_thresh: float = 1.0, min_eig: float = 0.0, max_residual: float = 255.0):
+    """fp_lk_track: pyramid from lk_pyramid(frames, levels, radius) of T frames of H x W, queries f32 [N,3] = (t, x, y) ->
+    (tracks f32 [T,N,2], visibility u8 [T,N], diagnostics f32 [T,N,4] = forward-backward distance, eigenvalue, residual, flags), all on
+    the device; nothing is synchronised.  The algorithm: include/freepose_hip.h, DESIGN.md §18."""
+    lib = _lib.load()
+    q = _dev(torch.as_tensor(queries), torch.float32)
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError(f"lk_track: queries {tuple(q.shape)} ([N,3] = (t, x, y))")
+    if not (pyramid.is_cuda and pyramid.dtype == torch.float32 and pyramid.is_contiguous()):
+        raise ValueError("lk_track: the pyramid is the float32 device tensor lk_pyramid returns")
+    if 1 <= int(levels) <= LK_MAX_LEVELS and 1 <= int(radius) <= LK_MAX_RADIUS and T >= 1 and H >= 1 and W >= 1:
+        need = sum(T * h * w for h, w in lk_layout(H, W, levels, radius))
+        if pyramid.numel() < need:
+            raise ValueError(f"lk_track: pyramid of {pyramid.numel()} floats, {need} needed for T={T}, {H} x {W}, levels={levels}, radius={radius}")
+    N = int(q.shape[0])
+    Tn = max(int(T), 0)
+    tracks = torch.empty((Tn, N, 2), dtype=torch.float32, device=q.device)
+    vis = torch.empty((Tn, N), dtype=torch.uint8, device=q.device)
+    diag = torch.empty((Tn, N, 4), dtype=torch.float32, device=q.device)
+    check(lib.fp_lk_track(context(), ptr(pyramid), int(T), int(H), int(W), int(levels), ptr(q) if N else None, N, int(radius), int(iters),
+                          float(fb_thresh), float(min_eig), float(max_residual), ptr(tracks) if N else None, ptr(vis) if N else None,
+                          ptr(diag) if N else None, current_stream()), "fp_lk_track")
+    return tracks, vis, diag
+
+
 # ---- video velocity errors (csrc/video_eval.hip) ----------------------------------------------------
 VIDEO_META_LD, VIDEO_PARAM_LD = 20, 16                     # csrc/video_eval_core.h FP_VE_META_LD / FP_VE_PARAM_LD
 VIDEO_MAX_OFFSETS, VIDEO_MAX_SYM, VIDEO_MAX_TRACKS = 16, 1024, 65535

@@ -425,6 +425,40 @@ int fp_patch_points(fp_ctx* ctx, const double* d_samples, int S, const double* d
 int fp_pnp_epnp(fp_ctx* ctx, const double* d_pts3d, const double* d_pts2d, const uint8_t* d_vis, const double* d_K9, int B, int N,
                 double* d_out, void* stream);
 
+/* ---- the built-in point tracker: pyramidal Lucas-Kanade with a forward-backward check ------------------------ */
+/* A classical stand-in for the learned tracker the reference fetches from torch.hub (CoTracker2): Bouguet's pyramidal Lucas-Kanade, a
+ * different kind of tracker with no parity claim against the reference, and not pinned to OpenCV's calcOpticalFlowPyrLK either.  The
+ * algorithm is stated in DESIGN.md section 18 and csrc/lk_core.h and pinned to the numpy restatement tests/_lk_ref.py.
+ * fp_lk_pyramid: d_frames u8 [T,H,W,3] (RGB) -> d_pyramid f32, the levels back to back, level l = [T, h_l, w_l] with h_0 = H, w_0 = W,
+ * h_l = (h_{l-1} + 1) / 2.  Level 0 is Y = (77 R + 150 G + 29 B + 128) >> 8; level l is level l-1 under the separable [1 4 6 4 1] / 16,
+ * rows then columns, replicate border, even pixels kept: (((a + e) + 4 (b + d)) + 6 c) / 16 in fp32 without FMA, bit for bit a float32
+ * numpy restatement.  `levels` (1..8) is a request: a level whose smaller side is below 2 radius + 1 is dropped with all coarser ones,
+ * level 0 always stays; the buffer holds the sum of T h_l w_l floats over the kept levels (ops.lk_layout computes the same sizes).
+ * Refused with FP_ERR_INVALID and a message before anything is launched: null pointers, T outside 1..65535, H or W outside 1..16384, T H W above
+ * 2^30, radius outside 1..15, levels outside 1..8. */
+int fp_lk_pyramid(fp_ctx* ctx, const uint8_t* d_frames, int T, int H, int W, int levels, int radius, float* d_pyramid, void* stream);
+/* d_pyramid as written by fp_lk_pyramid with the same T, H, W, levels, radius; d_queries f32 [N,3] = (t, x, y) in pixels of level 0
+ * -> d_tracks f32 [T,N,2], d_vis u8 [T,N], d_diag f32 [T,N,4] = {forward-backward distance (px), smaller eigenvalue of G / window
+ * pixels, mean |A - B| at the final position, flags} of the chain step that wrote the row (flags: 1 distance above fb_thresh, 2
+ * eigenvalue below min_eig, 4 residual above max_residual, 8 outside the image, 16 lost earlier in the chain; the query's own row has
+ * zeros and flag 8 when the query lies outside).  Every row is written and every value is finite.
+ * A query's frame is int(t) held inside [0, T-1] and non-finite x, y become 0 (callers that want a refusal check on the host, as
+ * freepose_amd.tracker does).  The query's row holds (x, y), visible when inside [0, W-1] x [0, H-1].  Chains move frame to frame from
+ * t_q to T-1 and to 0: one LK run src -> dst from the chain's position, one back from the result; the step is good when the distance
+ * between the returned point and the chain's position is <= fb_thresh, the eigenvalue >= min_eig, the residual <= max_residual and the
+ * forward result inside the image; a row is visible when its step is good and the previous row of the chain was visible (loss is
+ * sticky; the position is carried on regardless).  One LK run: from the coarsest level down, the (2 radius + 1)^2 window of A around
+ * p / 2^l by bilinear sampling (coordinates clamped into the level first, so nothing is read outside the pyramid), gradients as half
+ * central differences of such samples, G, exactly `iters` updates v += G^-1 b, then g <- 2 (g + v); a level whose G has a determinant
+ * <= 0 or a smaller eigenvalue per pixel below 1e-4 contributes no update.  No early exit.
+ * One wave per (query, direction), at most T-1 launches on the stream, no synchronisation; the fp32 pyramid is sampled and everything
+ * else done in fp64 (chain positions in a [T,N,2] fp64 workspace of the context: d_tracks holds their float32 roundings, a chain never
+ * continues from a rounded value), sums in a fixed order, no atomics: two
+ * calls give the same bits.  Refused with FP_ERR_INVALID and a message before anything is launched: what fp_lk_pyramid refuses, N < 0 or
+ * above 2^20, iters outside 1..64.  N = 0 does nothing; T = 1 writes the query rows and launches no chain step. */
+int fp_lk_track(fp_ctx* ctx, const float* d_pyramid, int T, int H, int W, int levels, const float* d_queries, int N, int radius, int iters,
+                float fb_thresh, float min_eig, float max_residual, float* d_tracks, uint8_t* d_vis, float* d_diag, void* stream);
+
 /* ---- video evaluation: velocity errors of pose tracks ------------------------------------------------------ */
 /* The scorer of scripts/eval_videos.py:186-208, i.e. src/utils/video_evaluation.py: get_average_rot_errors_dt (:4-11, get_rot_errors and
  * rot_error_in_cframe :37-63), get_average_proj_errors_dt (:25-34, get_translation_errors_proj and project :80-109),
