@@ -606,9 +606,65 @@ extern "C" int fp_op_im2col_norm(const void* img, void* A, int B, int H, int W, 
 }
 extern "C" int fp_op_layernorm(const void* X, void* Y, const void* g, const void* b, int rows, int D, float eps,
                                void* stream) {
+    if (rows == 0) return FP_OK;   // an empty tensor has no address
     FP_REQUIRE(X && Y && g && b, "op_layernorm: null argument");
     return fp_layernorm((const bf16_t*)X, (bf16_t*)Y, (const bf16_t*)g, (const bf16_t*)b, rows, D, eps, 0, 0, 0,
                         (hipStream_t)stream);
+}
+// The helper kernels of vit_misc.hip one at a time: argument checks, then the launcher the towers call.  An empty call (no rows, no
+// elements) returns before any launcher; everything the kernels cannot do is refused by the launchers' own checks, before a launch.
+extern "C" int fp_op_layernorm_rows(const void* X, void* Y, const void* g, const void* b, int rows, int D, float eps, int rows_per_b,
+                                    int in_stride_b, int in_off, int l2_normalize, void* stream) {
+    FP_REQUIRE(rows >= 0 && D >= 0, "op_layernorm_rows: rows=%d, D=%d", rows, D);
+    if (rows == 0 || D == 0) return FP_OK;
+    FP_REQUIRE(X && Y && g && b, "op_layernorm_rows: null argument");
+    FP_REQUIRE(rows_per_b <= 0 || (in_stride_b >= 0 && in_off >= 0), "op_layernorm_rows: in_stride_b=%d, in_off=%d (>= 0)", in_stride_b, in_off);
+    return fp_layernorm((const bf16_t*)X, (bf16_t*)Y, (const bf16_t*)g, (const bf16_t*)b, rows, D, eps, rows_per_b, in_stride_b, in_off,
+                        (hipStream_t)stream, l2_normalize != 0);
+}
+extern "C" int fp_op_posembed_aa(const void* src, void* dst, int G, int gh, int gw, int D, void* stream) {
+    FP_REQUIRE(G >= 0 && gh >= 0 && gw >= 0 && D >= 0, "op_posembed_aa: G=%d, gh=%d, gw=%d, D=%d", G, gh, gw, D);
+    if (gh == 0 || gw == 0 || D == 0) return FP_OK;
+    FP_REQUIRE(src && dst, "op_posembed_aa: null argument");
+    return fp_posembed_aa((const bf16_t*)src, (bf16_t*)dst, G, gh, gw, D, (hipStream_t)stream);
+}
+extern "C" int fp_op_token_init(void* X, const void* cls, const void* pos0, const void* reg, int nreg, int B, int n_tok, int npad, int D,
+                                void* stream) {
+    FP_REQUIRE(B >= 0 && B <= 65535 && D >= 0, "op_token_init: B=%d (0..65535), D=%d", B, D);
+    FP_REQUIRE(nreg >= 0 && n_tok >= 1 + nreg && npad >= n_tok, "op_token_init: nreg=%d, n_tok=%d, npad=%d (1 + nreg <= n_tok <= npad)", nreg, n_tok,
+               npad);
+    if (B == 0 || D == 0) return FP_OK;
+    FP_REQUIRE(X && cls && pos0 && (reg || nreg == 0), "op_token_init: null argument");
+    FP_REQUIRE((long long)(1 + nreg + npad - n_tok) * D <= INT32_MAX, "op_token_init: %d rows of %d elements", 1 + nreg + npad - n_tok, D);
+    return fp_token_init((bf16_t*)X, (const bf16_t*)cls, (const bf16_t*)pos0, (const bf16_t*)reg, nreg, B, n_tok, npad, D, (hipStream_t)stream);
+}
+extern "C" int fp_op_row_stats(const void* X, int rows, int D, float eps, void* d_rec, float* d_rstd, void* stream) {
+    FP_REQUIRE(rows >= 0 && D >= 0, "op_row_stats: rows=%d, D=%d", rows, D);
+    if (rows == 0) return FP_OK;
+    FP_REQUIRE(X && d_rec && d_rstd, "op_row_stats: null argument");
+    FP_REQUIRE(D > 0, "op_row_stats: D=%d", D);
+    return fp_row_stats((const bf16_t*)X, (uint4*)d_rec, d_rstd, rows, D, eps, (hipStream_t)stream);
+}
+extern "C" int fp_op_stats_finalize(const void* part, int rows, int D, float eps, int part_ld, void* d_rec, float* d_rstd, void* stream) {
+    FP_REQUIRE(rows >= 0 && D >= 0, "op_stats_finalize: rows=%d, D=%d", rows, D);
+    if (rows == 0) return FP_OK;
+    FP_REQUIRE(part && d_rec && d_rstd, "op_stats_finalize: null argument");
+    FP_REQUIRE(D > 0 && (part_ld == 0 || part_ld >= rows), "op_stats_finalize: D=%d, part_ld=%d (0 or >= rows=%d)", D, part_ld, rows);
+    return fp_stats_finalize((const float2*)part, (uint4*)d_rec, d_rstd, rows, D, eps, (hipStream_t)stream, part_ld);
+}
+extern "C" int fp_op_ln_fold(const void* W, const void* gamma, const void* beta, const void* bias, int N, int K, int n_scaled, float row_scale,
+                             void* Wf, void* d_cb, void* stream) {
+    FP_REQUIRE(N >= 0 && K >= 0, "op_ln_fold: N=%d, K=%d", N, K);
+    if (N == 0) return FP_OK;
+    FP_REQUIRE(K > 0 && n_scaled >= 0 && n_scaled <= N, "op_ln_fold: K=%d, n_scaled=%d outside [0, N=%d]", K, n_scaled, N);
+    return fp_ln_fold((const bf16_t*)W, (const bf16_t*)gamma, (const bf16_t*)beta, (const bf16_t*)bias, (bf16_t*)Wf, (uint4*)d_cb, N, K, n_scaled,
+                      row_scale, (hipStream_t)stream);
+}
+extern "C" int fp_op_transpose(const void* src, void* dst, int rows, int cols, void* stream) {
+    FP_REQUIRE(rows >= 0 && cols >= 0, "op_transpose: rows=%d, cols=%d", rows, cols);
+    if (rows == 0 || cols == 0) return FP_OK;
+    FP_REQUIRE(src && dst, "op_transpose: null argument");
+    return fp_transpose_bf16((const bf16_t*)src, (bf16_t*)dst, rows, cols, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

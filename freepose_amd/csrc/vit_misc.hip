@@ -448,6 +448,7 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const bf16_t* __restrict__
 
 int fp_row_stats(const bf16_t* X, uint4* ms, float* rstd, int rows, int D, float eps, hipStream_t s) {
     FP_REQUIRE(D % 8 == 0 && D <= 8 * 64 * 3, "row_stats: D=%d unsupported", D);
+    if (rows <= 0) return FP_OK;   // no rows: nothing to launch (a grid of 0 workgroups is a launch error)
     const int blocks = std::min(cdiv(rows, 4), 256 * 8);
     if (D <= 512) hipLaunchKernelGGL(row_stats_kernel<1>, dim3(blocks), dim3(256), 0, s, X, ms, rstd, rows, D, eps);
     else if (D <= 1024) hipLaunchKernelGGL(row_stats_kernel<2>, dim3(blocks), dim3(256), 0, s, X, ms, rstd, rows, D, eps);
@@ -458,6 +459,7 @@ int fp_row_stats(const bf16_t* X, uint4* ms, float* rstd, int rows, int D, float
 
 int fp_stats_finalize(const float2* part, uint4* ms, float* rstd, int rows, int D, float eps, hipStream_t s, int part_ld) {
     FP_REQUIRE(D % 64 == 0, "stats_finalize: D=%d must be a multiple of 64", D);
+    if (rows <= 0) return FP_OK;
     hipLaunchKernelGGL(stats_finalize_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, s, part, ms, rstd, rows, D / 64, 1.0f / (float)D, eps, part_ld > 0 ? part_ld : rows);
     FP_LAUNCH_CHECK();
     return FP_OK;
@@ -487,6 +489,7 @@ int fp_im2col_norm_ms(const bf16_t* img, bf16_t* A, int B, int H, int W, int ps,
 int fp_token_init(bf16_t* X, const bf16_t* cls, const bf16_t* pos0, const bf16_t* reg, int nreg, int B,
                   int n_tok, int npad, int D, hipStream_t s) {
     const int nrows = 1 + nreg + (npad - n_tok);
+    if (B <= 0 || D <= 0) return FP_OK;
     hipLaunchKernelGGL(token_init_kernel, dim3(cdiv(nrows * D, 256), B), dim3(256), 0, s, X, cls, pos0, reg, nreg,
                        n_tok, npad, D);
     FP_LAUNCH_CHECK();
@@ -496,13 +499,15 @@ int fp_token_init(bf16_t* X, const bf16_t* cls, const bf16_t* pos0, const bf16_t
 int fp_layernorm(const bf16_t* X, bf16_t* Y, const bf16_t* gamma, const bf16_t* beta, int rows, int D, float eps,
                  int rows_per_b, int in_stride_b, int in_off, hipStream_t s, int l2_normalize) {
     FP_REQUIRE(D % 8 == 0 && D <= 8 * 64 * 4, "layernorm: D=%d unsupported", D);
+    FP_REQUIRE(!l2_normalize || D <= 8 * 64 * 3, "layernorm: D=%d with l2_normalize unsupported", D);
+    if (rows <= 0) return FP_OK;   // no rows: nothing to launch
     if (rows_per_b <= 0) { rows_per_b = rows; in_stride_b = 0; in_off = 0; }
     const int blocks = std::min(cdiv(rows, 4), 256 * 8);
 #define FP_LN(C, L) hipLaunchKernelGGL((layernorm_kernel<C, L>), dim3(blocks), dim3(256), 0, s, X, Y, gamma, beta, rows, D, eps, rows_per_b, in_stride_b, in_off)
     if (D <= 512) { if (l2_normalize) FP_LN(1, 1); else FP_LN(1, 0); }
     else if (D <= 1024) { if (l2_normalize) FP_LN(2, 1); else FP_LN(2, 0); }
     else if (D <= 1536) { if (l2_normalize) FP_LN(3, 1); else FP_LN(3, 0); }
-    else { FP_REQUIRE(!l2_normalize, "layernorm: D=%d with l2_normalize unsupported", D); FP_LN(4, 0); }   // CLIP ViT-bigG/14: 1664
+    else FP_LN(4, 0);   // CLIP ViT-bigG/14: 1664 (never with l2_normalize: refused above)
 #undef FP_LN
     FP_LAUNCH_CHECK();
     return FP_OK;
@@ -535,6 +540,7 @@ int fp_ffa_pool(const bf16_t* feats, const uint8_t* mask, bf16_t* out, float* ou
 
 int fp_transpose_bf16(const bf16_t* src, bf16_t* dst, int rows, int cols, hipStream_t s) {
     const size_t total = (size_t)rows * cols;
+    if (total == 0) return FP_OK;
     hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, src, dst, rows, cols);
     FP_LAUNCH_CHECK();
     return FP_OK;

@@ -1372,6 +1372,110 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     return y
 
 
+def layernorm_rows(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-6, rows: Optional[int] = None,
+                   rows_per_b: int = 0, in_stride_b: int = 0, in_off: int = 0, l2_normalize: bool = False) -> torch.Tensor:
+    """fp_op_layernorm_rows on x bf16 [n, D]: `rows` output rows (default n), output row r from input row
+    (r // rows_per_b) * in_stride_b + in_off + r % rows_per_b (rows_per_b 0: row r); l2_normalize: every row F.normalize()d"""
+    lib = _lib.load()
+    x, gamma, beta = _dev(x, torch.bfloat16), _dev(gamma, torch.bfloat16), _dev(beta, torch.bfloat16)
+    n, D = x.shape
+    rows = n if rows is None else int(rows)
+    if rows_per_b > 0 and rows > 0:
+        nb = (rows - 1) // rows_per_b                      # the last, possibly partial, batch; the one before it is whole
+        last = nb * in_stride_b + in_off + (rows - 1) % rows_per_b
+        whole = (nb - 1) * in_stride_b + in_off + rows_per_b - 1 if nb else 0
+        assert min(in_stride_b, in_off) >= 0 and max(last, whole) < n, f"layernorm_rows: the gather reads past row {n - 1}"
+    else:
+        assert rows <= n
+    context()
+    y = torch.empty((rows, D), dtype=torch.bfloat16, device=x.device)
+    check(lib.fp_op_layernorm_rows(ptr(x), ptr(y), ptr(gamma), ptr(beta), rows, D, float(eps), int(rows_per_b), int(in_stride_b), int(in_off),
+                                   int(bool(l2_normalize)), current_stream()), "fp_op_layernorm_rows")
+    return y
+
+
+def posembed_aa(grid: torch.Tensor, gh: int, gw: int) -> torch.Tensor:
+    """grid bf16 [G*G, D] -> [gh*gw, D]: the bicubic antialiased resize of the ViT's position embedding (fp_op_posembed_aa)"""
+    lib = _lib.load()
+    grid = _dev(grid, torch.bfloat16)
+    n, D = grid.shape
+    G = int(round(n ** 0.5))
+    assert G * G == n, f"posembed_aa: {n} rows are no square grid"
+    context()
+    out = torch.empty((gh * gw, D), dtype=torch.bfloat16, device=grid.device)
+    check(lib.fp_op_posembed_aa(ptr(grid), ptr(out), G, int(gh), int(gw), D, current_stream()), "fp_op_posembed_aa")
+    return out
+
+
+def token_init(x: torch.Tensor, cls: torch.Tensor, pos0: torch.Tensor, reg: Optional[torch.Tensor], n_tok: int) -> torch.Tensor:
+    """in place on the token buffer x bf16 [B, npad, D] (contiguous, on the device): row 0 = cls + pos0, rows 1..nreg = reg [nreg, D],
+    rows [n_tok, npad) = 0 (fp_op_token_init)"""
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 3
+    B, npad, D = x.shape
+    cls, pos0 = _dev(cls, torch.bfloat16).reshape(-1), _dev(pos0, torch.bfloat16).reshape(-1)
+    nreg = 0 if reg is None else int(reg.shape[0])
+    reg = _dev(reg, torch.bfloat16) if nreg else None
+    assert cls.numel() == D and pos0.numel() == D and (reg is None or tuple(reg.shape) == (nreg, D))
+    context()
+    check(lib.fp_op_token_init(ptr(x), ptr(cls), ptr(pos0), ptr(reg), nreg, B, int(n_tok), npad, D, current_stream()), "fp_op_token_init")
+    return x
+
+
+def row_stats(x: torch.Tensor, eps: float = 1e-6):
+    """statistics of the folded LayerNorm from the rows x bf16 [rows, D] (fp_op_row_stats): (records i32 [rows, 4], rstd f32 [rows]);
+    a record is bf16 {sh, sl, sh, -mh, -ml, -mh, 0, 0}: sigma = sh + sl, mean = -(mh + ml)"""
+    lib = _lib.load()
+    x = _dev(x, torch.bfloat16)
+    rows, D = x.shape
+    context()
+    rec = torch.empty((rows, 4), dtype=torch.int32, device=x.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    check(lib.fp_op_row_stats(ptr(x), rows, D, float(eps), ptr(rec), ptr(rstd), current_stream()), "fp_op_row_stats")
+    return rec, rstd
+
+
+def stats_finalize(part: torch.Tensor, rows: int, eps: float = 1e-6):
+    """the same from partial sums part f32 [D / 64, part_ld, 2] = (sum x, sum x^2) per 64-column block, part_ld >= rows
+    (fp_op_stats_finalize): (records i32 [rows, 4], rstd f32 [rows])"""
+    lib = _lib.load()
+    part = _dev(part, torch.float32)
+    nb, part_ld, two = part.shape
+    assert two == 2 and part_ld >= rows
+    context()
+    rec = torch.empty((rows, 4), dtype=torch.int32, device=part.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=part.device)
+    check(lib.fp_op_stats_finalize(ptr(part), int(rows), nb * 64, float(eps), part_ld, ptr(rec), ptr(rstd), current_stream()),
+          "fp_op_stats_finalize")
+    return rec, rstd
+
+
+def ln_fold(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: torch.Tensor, n_scaled: int = 0, row_scale: float = 1.0):
+    """the weight side of the folded LayerNorm (fp_op_ln_fold): (Wf bf16 [N, K], records i32 [N, 4] = bf16 {b'h, b'h, b'l, ch, ch, cl, 0, 0})"""
+    lib = _lib.load()
+    w, bias = _dev(w, torch.bfloat16), _dev(bias, torch.bfloat16)
+    gamma, beta = _dev(gamma, torch.bfloat16), _dev(beta, torch.bfloat16)
+    N, K = w.shape
+    assert gamma.numel() == K and beta.numel() == K and bias.numel() == N
+    context()
+    wf = torch.empty_like(w)
+    cb = torch.empty((N, 4), dtype=torch.int32, device=w.device)
+    check(lib.fp_op_ln_fold(ptr(w), ptr(gamma), ptr(beta), ptr(bias), N, K, int(n_scaled), float(row_scale), ptr(wf), ptr(cb),
+                            current_stream()), "fp_op_ln_fold")
+    return wf, cb
+
+
+def transpose(x: torch.Tensor) -> torch.Tensor:
+    """x bf16 [rows, cols] -> [cols, rows] (fp_op_transpose)"""
+    lib = _lib.load()
+    x = _dev(x, torch.bfloat16)
+    rows, cols = x.shape
+    context()
+    out = torch.empty((cols, rows), dtype=torch.bfloat16, device=x.device)
+    check(lib.fp_op_transpose(ptr(x), ptr(out), rows, cols, current_stream()), "fp_op_transpose")
+    return out
+
+
 def plan_vit_batches(n: int, n_tok: int, max_batch: int = 192, n_cu: int = 256) -> list:
     return list(_plan_vit_batches(int(n), int(n_tok), int(max_batch), int(n_cu)))
 

@@ -326,6 +326,33 @@ int fp_op_layernorm(const void* d_X, void* d_Y, const void* d_gamma, const void*
  * patch unfold of bf16 crops [B,3,H,W] in [0,1] into the patch-embed GEMM's A operand [B*(H/ps)*(W/ps), KP], k = c*ps*ps + dy*ps + dx,
  * columns >= 3*ps*ps zero (the Conv2d patch_embed.proj of hub DINOv2 behind dino.py:18).  Kernel-level entry used by the tests. */
 int fp_op_im2col_norm(const void* d_img, void* d_A, int B, int H, int W, int ps, int KP, void* stream);
+/* The other helper kernels of the towers, one at a time (kernel-level entries used by the tests).  All tensors bf16 unless said
+ * otherwise; a call with no rows / no elements returns 0 without launching anything.
+ * fp_op_layernorm with the launch form of the towers' final norm: output row r reads input row
+ * (r / rows_per_b) * in_stride_b + in_off + r % rows_per_b (rows_per_b <= 0: row r); l2_normalize != 0 writes every row
+ * F.normalize()d with fp_l2_normalize's arithmetic (D <= 1536).  D: a multiple of 8 up to 2048. */
+int fp_op_layernorm_rows(const void* d_X, void* d_Y, const void* d_gamma, const void* d_beta, int rows, int D, float eps, int rows_per_b,
+                         int in_stride_b, int in_off, int l2_normalize, void* stream);
+/* bicubic (a = -0.5) antialiased resize of a position-embedding grid, d_src [G*G, D] -> d_dst [gh*gw, D] (hub DINOv2
+ * interpolate_pos_encoding: F.interpolate(mode="bicubic", antialias=True) on the channel-last grid), fp32 arithmetic. */
+int fp_op_posembed_aa(const void* d_src, void* d_dst, int G, int gh, int gw, int D, void* stream);
+/* the rows of the token buffer d_X [B, npad, D] that the patch-embed GEMM does not write: row 0 = bf16(cls + pos0), rows 1..nreg = the
+ * register tokens d_reg [nreg, D] (no position), rows [n_tok, npad) = 0.  Rows 1 + nreg .. n_tok - 1 are not touched. */
+int fp_op_token_init(void* d_X, const void* d_cls, const void* d_pos0, const void* d_reg, int nreg, int B, int n_tok, int npad, int D,
+                     void* stream);
+/* row statistics of the folded LayerNorm straight from the rows d_X [rows, D] (D a multiple of 8 up to 1536): d_rec u32 [rows,4] the
+ * row records and d_rstd f32 [rows] = 1 / sigma, layout as in fp_op_gemm_stats. */
+int fp_op_row_stats(const void* d_X, int rows, int D, float eps, void* d_rec, float* d_rstd, void* stream);
+/* the same records from per-64-column partial sums d_part f32 [D/64, part_ld, 2] = (sum x, sum x^2) of row m at [nb, m], added in
+ * block order (what the LS_RES_STATS epilogue writes); part_ld >= rows, 0 = rows; D a multiple of 64. */
+int fp_op_stats_finalize(const void* d_part, int rows, int D, float eps, int part_ld, void* d_rec, float* d_rstd, void* stream);
+/* the weight side of the folded LayerNorm (fp_op_ln_linear): d_Wf [N,K] = bf16(W diag(gamma) s_n), s_n = row_scale for n < n_scaled and 1
+ * otherwise; d_cb u32 [N,4] = bf16 {b'h, b'h, b'l, ch, ch, cl, 0, 0}, two-piece splits of b' = (bias + W beta) s_n and of
+ * c = sum_k Wf[n,k] (over the ROUNDED Wf).  K a multiple of 8. */
+int fp_op_ln_fold(const void* d_W, const void* d_gamma, const void* d_beta, const void* d_bias, int N, int K, int n_scaled, float row_scale,
+                  void* d_Wf, void* d_cb, void* stream);
+/* d_dst [cols, rows] = d_src [rows, cols]^T */
+int fp_op_transpose(const void* d_src, void* d_dst, int rows, int cols, void* stream);
 
 /* attention forward for a general head dimension on the plain output of one bias GEMM with N = 3 * width: QKV [B*npad, 3*heads*head_dim]
  * (ldqkv elements), columns [q | k | v], each heads x head_dim (nn.MultiheadAttention's in_proj order) -> O [B*npad, heads*head_dim]
