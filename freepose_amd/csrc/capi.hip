@@ -48,14 +48,7 @@ extern "C" int fp_lab_read_scratch(fp_ctx* ctx, void* host, size_t bytes) {
     return FP_OK;
 }
 // lab build only: copy a named workspace of the context to the host (raster.dbg: the tile kernel's phase clocks)
-extern "C" int fp_lab_read_buffer(fp_ctx* ctx, const char* name, void* host, size_t bytes) {
-    FP_REQUIRE(ctx && name && host, "lab_read_buffer: null argument");
-    auto it = ctx->bufs.find(name);
-    FP_REQUIRE(it != ctx->bufs.end() && it->second.bytes >= bytes, "lab_read_buffer: no such buffer");
-    FP_HIP(hipDeviceSynchronize());
-    FP_HIP(hipMemcpy(host, it->second.p, bytes, hipMemcpyDeviceToHost));
-    return FP_OK;
-}
+extern "C" int fp_lab_read_buffer(fp_ctx* ctx, const char* name, void* host, size_t bytes) { return fp_op_workspace_read(ctx, name, host, bytes); }
 #endif
 
 extern "C" int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value) {
@@ -570,6 +563,43 @@ extern "C" int fp_op_ln_chain(fp_ctx* ctx, const void* X1, int K1, const void* W
     if ((rc = cons.run(ctx, s))) return rc;
     FP_HIP(hipMemcpyAsync(d_mfrag, st.stat, (size_t)M * sizeof(uint4), hipMemcpyDeviceToDevice, s));
     FP_HIP(hipMemcpyAsync(d_rstd, st.rstd, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return FP_OK;
+}
+// One LN-folded consumer on row records the CALLER supplies (d_mfrag u32 [M,4], d_rstd f32 [M]: what fp_op_ln_chain, fp_op_row_stats or
+// fp_op_stats_finalize returned) — the second consumer of a set of records, the way fp_vit_forward's transposed-V launch reads the records
+// the qk launch made out of fc2's sums.  fold W' / (colsum, b') -> the LN-folded GEMM; mode 0: bias, 1: bias + GELU, 2: transposed V
+// store (ldo unused).  Nothing is recomputed from the rows of X.
+extern "C" int fp_op_ln_consume(fp_ctx* ctx, const void* X, int M, int K, const void* g_ln, const void* b_ln, const void* W, int N,
+                                const void* bias, int mode, int npad, int heads, int n_scaled, float row_scale, const void* d_mfrag,
+                                const float* d_rstd, void* out, int ldo, void* stream) {
+    FP_REQUIRE(ctx && X && g_ln && b_ln && W && bias && d_mfrag && d_rstd && out, "op_ln_consume: null argument");
+    FP_REQUIRE(mode >= 0 && mode <= 2, "op_ln_consume: mode %d (0..2)", mode);
+    FP_REQUIRE(M > 0 && K > 0 && K % 64 == 0 && n_scaled >= 0 && n_scaled <= N && (mode == 2 || ldo >= N), "op_ln_consume: M=%d K=%d N=%d ldo=%d n_scaled=%d",
+               M, K, N, ldo, n_scaled);
+    FP_REQUIRE(mode != 2 || (npad > 0 && M % npad == 0 && heads > 0 && N == heads * 64), "op_ln_consume: M=%d N=%d npad=%d heads=%d (M %% npad == 0, N == 64 heads)",
+               M, N, npad, heads);
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t* Wf;
+    uint4* cb;
+    // the records are the caller's: eps went into them, no sums are pending
+    LnStats st{(uint4*)d_mfrag, (float*)d_rstd, nullptr, M, K, 0.0f};
+    int rc;
+    FP_WS(ctx, "op.ln_wf", (size_t)N * K * 2, Wf);
+    FP_WS(ctx, "op.ln_cb", (size_t)N * sizeof(uint4), cb);
+    if ((rc = fp_ln_fold((const bf16_t*)W, (const bf16_t*)g_ln, (const bf16_t*)b_ln, (const bf16_t*)bias, Wf, cb, N, K, n_scaled, row_scale, s))) return rc;
+    GemmStep t((const bf16_t*)X, K, Wf, K, (bf16_t*)out, ldo, (const bf16_t*)bias, M, N, mode == 1);
+    if (mode == 2) t.transposed_v(npad, heads);
+    if ((rc = st.attach(t, cb))) return rc;
+    return t.run(ctx, s);
+}
+// Copies the first `bytes` bytes of the context workspace `name` ("vit.x", "clip.qkv", ...) to the host, behind everything the device has
+// been given: what a tower left in its buffers, for the tests that replay a forward step by step.
+extern "C" int fp_op_workspace_read(fp_ctx* ctx, const char* name, void* host, size_t bytes) {
+    FP_REQUIRE(ctx && name && host, "op_workspace_read: null argument");
+    auto it = ctx->bufs.find(name);
+    FP_REQUIRE(it != ctx->bufs.end() && it->second.bytes >= bytes, "op_workspace_read: no workspace '%s' of at least %zu bytes", name, bytes);
+    FP_HIP(hipDeviceSynchronize());
+    FP_HIP(hipMemcpy(host, it->second.p, bytes, hipMemcpyDeviceToHost));
     return FP_OK;
 }
 // y = bf16(gelu_erf(x)) elementwise with the direct fp32 expression — the DEFINITION the fc1 epilogue's table is filled from; the

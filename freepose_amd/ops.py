@@ -1080,6 +1080,74 @@ def gemm_stats(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, gamma: torc
     return out, stat
 
 
+def gemm_patch(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, pos: torch.Tensor, tokens: torch.Tensor, tok_off: int) -> torch.Tensor:
+    """the patch-embed GEMM (fp_op_gemm_patch), in place on the token buffer tokens bf16 [B, npad, D]: row b * P + p of x [B * P, K] lands
+    in tokens[b, tok_off + p] as bf16(bf16(x w^T + bias) + pos[p]), pos bf16 [P, D]; the other rows are not touched"""
+    lib = _lib.load()
+    x, w, bias, pos = _dev(x, torch.bfloat16), _dev(w, torch.bfloat16), _dev(bias, torch.bfloat16), _dev(pos, torch.bfloat16)
+    assert tokens.is_cuda and tokens.dtype == torch.bfloat16 and tokens.is_contiguous() and tokens.dim() == 3
+    B, npad, D = tokens.shape
+    M, K = x.shape
+    P = pos.shape[0]
+    assert tuple(w.shape) == (D, K) and tuple(pos.shape) == (P, D) and bias.numel() == D and M == B * P
+    check(lib.fp_op_gemm_patch(context(), ptr(x), K, ptr(w), K, ptr(tokens), D, ptr(bias), ptr(pos), M, D, K, P, npad, int(tok_off),
+                               current_stream()), "fp_op_gemm_patch")
+    return tokens
+
+
+def ln_chain(x1: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, gamma: torch.Tensor, resid: torch.Tensor, g_ln: torch.Tensor,
+             b_ln: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, mode: int = 0, route: int = 0, eps: float = 1e-6, n_scaled: int = 0,
+             row_scale: float = 1.0):
+    """producer -> consumer pair of the folded LayerNorm (fp_op_ln_chain): y = resid + gamma * (x1 w1^T + b1) with the row sums of y from
+    the epilogue, out = LN(y) w2^T + b2 (mode 0) or its GELU (mode 1).  route 0: the sums are finalised by their own kernel, 1: the
+    consumer launch takes them along.  Returns (y, out, records i32 [M, 4], rstd f32 [M])"""
+    lib = _lib.load()
+    x1, w1, b1 = _dev(x1, torch.bfloat16), _dev(w1, torch.bfloat16), _dev(b1, torch.bfloat16)
+    gamma, resid = _dev(gamma, torch.bfloat16), _dev(resid, torch.bfloat16)
+    g_ln, b_ln, w2, b2 = _dev(g_ln, torch.bfloat16), _dev(b_ln, torch.bfloat16), _dev(w2, torch.bfloat16), _dev(b2, torch.bfloat16)
+    M, K1 = x1.shape
+    D, N2 = w1.shape[0], w2.shape[0]
+    assert tuple(w1.shape) == (D, K1) and tuple(resid.shape) == (M, D) and tuple(w2.shape) == (N2, D)
+    assert b1.numel() == D and gamma.numel() == D and g_ln.numel() == D and b_ln.numel() == D and b2.numel() == N2
+    y = torch.empty((M, D), dtype=torch.bfloat16, device=x1.device)
+    out = torch.empty((M, N2), dtype=torch.bfloat16, device=x1.device)
+    rec = torch.empty((M, 4), dtype=torch.int32, device=x1.device)
+    rstd = torch.empty((M,), dtype=torch.float32, device=x1.device)
+    check(lib.fp_op_ln_chain(context(), ptr(x1), K1, ptr(w1), ptr(b1), ptr(gamma), ptr(resid), ptr(y), M, D, ptr(g_ln), ptr(b_ln), float(eps),
+                             ptr(w2), N2, ptr(b2), int(mode), int(n_scaled), float(row_scale), int(route), ptr(out), N2, ptr(rec), ptr(rstd),
+                             current_stream()), "fp_op_ln_chain")
+    return y, out, rec, rstd
+
+
+def ln_consume(x: torch.Tensor, rec: torch.Tensor, rstd: torch.Tensor, g_ln: torch.Tensor, b_ln: torch.Tensor, w: torch.Tensor,
+               bias: torch.Tensor, mode: int = 0, npad: int = 0, heads: int = 0, n_scaled: int = 0, row_scale: float = 1.0) -> torch.Tensor:
+    """ln_linear on row records the caller supplies (fp_op_ln_consume): rec i32 [M, 4], rstd f32 [M] as ln_chain, row_stats or
+    stats_finalize return them — a further consumer of the same rows, e.g. the ViT's transposed-V launch (mode 2) behind its qk launch"""
+    lib = _lib.load()
+    x, w, bias = _dev(x, torch.bfloat16), _dev(w, torch.bfloat16), _dev(bias, torch.bfloat16)
+    g_ln, b_ln = _dev(g_ln, torch.bfloat16), _dev(b_ln, torch.bfloat16)
+    rec, rstd = _dev(rec, torch.int32), _dev(rstd, torch.float32)
+    M, K = x.shape
+    N = w.shape[0]
+    assert tuple(rec.shape) == (M, 4) and tuple(rstd.shape) == (M,) and w.shape[1] == K and bias.numel() == N
+    if mode == 2:
+        out = torch.zeros((M // npad, heads, 64, npad), dtype=torch.bfloat16, device=x.device)
+    else:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    check(lib.fp_op_ln_consume(context(), ptr(x), M, K, ptr(g_ln), ptr(b_ln), ptr(w), N, ptr(bias), int(mode), int(npad), int(heads),
+                               int(n_scaled), float(row_scale), ptr(rec), ptr(rstd), ptr(out), N, current_stream()), "fp_op_ln_consume")
+    return out
+
+
+def workspace_read(name: str, shape, dtype=torch.bfloat16, device: Optional[int] = None) -> torch.Tensor:
+    """the head of the context workspace `name` ("vit.x", "clip.qkv", ...: what the last tower forward left there) as a host tensor of
+    `shape` and `dtype` (fp_op_workspace_read); raises when the context has no such workspace or it is shorter"""
+    out = torch.empty(tuple(int(v) for v in shape), dtype=dtype)
+    if out.numel():
+        check(_lib.load().fp_op_workspace_read(context(device), name.encode(), ptr(out), out.numel() * out.element_size()), "fp_op_workspace_read")
+    return out
+
+
 ATTN_QSCALE = 1.4426950408889634 / 8.0   # log2(e) / sqrt(64): what q_prescaled=True expects the q columns to carry
 
 

@@ -311,6 +311,18 @@ int fp_op_ln_chain(fp_ctx* ctx, const void* d_X1, int K1, const void* d_W1, cons
                    void* d_Y, int M, int D, const void* d_g_ln, const void* d_b_ln, float eps, const void* d_W2, int N2,
                    const void* d_b2, int mode, int n_scaled, float row_scale, int route, void* d_out, int ldo, void* d_mfrag,
                    float* d_rstd, void* stream);
+/* One LN-folded consumer (fp_op_ln_linear's modes 0, 1, 2) on row records the caller supplies instead of records recomputed from the
+ * rows: d_mfrag u32 [M,4] and d_rstd f32 [M] as fp_op_ln_chain, fp_op_row_stats or fp_op_stats_finalize return them.  This is how
+ * fp_vit_forward's transposed-V launch of a block reads the records the qk launch of the same block wrote.  d_out: bf16 [M,N] with ldo
+ * elements per row (modes 0, 1) or Vt [M/npad, heads, 64, npad] (mode 2, N == 64 * heads; ldo unused).  K % 64 == 0.  Kernel-level entry
+ * used by the tests. */
+int fp_op_ln_consume(fp_ctx* ctx, const void* d_X, int M, int K, const void* d_g_ln, const void* d_b_ln, const void* d_W, int N,
+                     const void* d_bias, int mode, int npad, int heads, int n_scaled, float row_scale, const void* d_mfrag,
+                     const float* d_rstd, void* d_out, int ldo, void* stream);
+/* copies the first `bytes` bytes of the context's named workspace (the buffers a tower forward leaves behind: "vit.x", "vit.qk",
+ * "clip.qkv", "clip_text.pool", ...) to host memory, after a device synchronisation; an unknown name or a workspace shorter than `bytes`
+ * is an error.  Host-only entry used by the tests that replay a forward step by step. */
+int fp_op_workspace_read(fp_ctx* ctx, const char* name, void* host, size_t bytes);
 /* d_y[i] = bf16(0.5 x (1 + erf(x / sqrt 2))) elementwise on bf16 values in fp32: the direct expression the fc1 epilogue's GELU table
  * is filled from (hub DINOv2 Mlp act_layer = nn.GELU behind src/pipeline/retrieval/dino.py:18-19); the table-GELU GEMM is tested
  * against it on all 65 536 bf16 inputs */

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests._tower_replay import massive_state_dict as _massive_state_dict    # shared with tests/test_gpu_tower_replay.py
+
 pytestmark = pytest.mark.gpu
 
 
@@ -58,31 +60,6 @@ def test_vit_forward_vs_fp32_oracle(model, H, layer, B):
         cg, rg = _metrics(got, ref32)
         print(f"torch-bf16 vs fp32: cos {c16:.5f} rel {r16:.4f} | hip vs fp32: cos {cg:.5f} rel {rg:.4f}")
         assert rg <= 2.0 * r16 + 2e-3
-
-
-def _massive_state_dict(model, seed):
-    """random-init weights bent towards what trained DINOv2-reg checkpoints look like (parity caveat i): a few residual
-    channels carry activations hundreds of times the typical magnitude at the CLS / register tokens and at a handful of patch
-    positions, LayerNorm gains span an order of magnitude with non-zero shifts, LayerScale gammas are small and uneven."""
-    from freepose_amd import ops
-    sd = {k: v.float() for k, v in ops.random_state_dict(model, seed=seed).items()}
-    g = torch.Generator().manual_seed(seed + 100)
-    dim = sd["norm.weight"].numel()
-    big = [5, dim // 3, dim - 7]
-    sd["cls_token"][..., big[0]] += 90.0
-    if "register_tokens" in sd:
-        sd["register_tokens"][..., big[1]] += 160.0
-        sd["register_tokens"][:, :2, big[2]] -= 70.0
-    sd["pos_embed"][:, 40:44, big[1]] += 220.0            # a few patch tokens with a massive channel
-    sd["pos_embed"][:, 300:302, big[0]] -= 130.0
-    for k in list(sd):
-        if k.endswith("norm1.weight") or k.endswith("norm2.weight") or k == "norm.weight":
-            sd[k] = torch.exp(torch.empty(dim).uniform_(-1.2, 1.0, generator=g))
-        elif k.endswith("norm1.bias") or k.endswith("norm2.bias") or k == "norm.bias":
-            sd[k] = torch.empty(dim).uniform_(-0.5, 0.5, generator=g)
-        elif k.endswith("gamma"):
-            sd[k] = torch.exp(torch.empty(dim).uniform_(-4.0, 0.0, generator=g))
-    return {k: v.to(torch.bfloat16) for k, v in sd.items()}
 
 
 @pytest.mark.parametrize("model,H,layer,B", [("dinov2_vits14_reg", 224, 22, 2), ("dinov2_vitl14_reg", 420, 22, 1)])
