@@ -77,12 +77,9 @@ int fp_ctx::get(const char* name, size_t bytes, void** out) {
     *out = b.p;
     return FP_OK;
 }
+#ifdef FP_LAB
 int fp_ctx::sk_scratch(FpGemmArgs& g, hipStream_t s) {
     g.sk_mode = opt_stream_k == 0 ? 1 : 0;
-#ifndef FP_LAB
-    g.sk_mode = 1;   // the balanced tier is compiled into the lab build only (gemm_bf16.hip): the product lends no scratch
-    (void)s;
-#endif
     if (g.sk_mode == 1) return FP_OK;
     if (!sk_ws) {
         FP_HIP(hipMalloc((void**)&sk_ws, SK_WS_BYTES));
@@ -94,9 +91,13 @@ int fp_ctx::sk_scratch(FpGemmArgs& g, hipStream_t s) {
     g.sk_cnt = sk_cnt; g.sk_cnt_n = SK_CNT_N;
     return FP_OK;
 }
+#endif
 int fp_ctx::gemm(FpGemmArgs& g, int epi, hipStream_t s) {
     g.no_split = opt_row_split == 0;   // fp_ctx_set_option(ctx, "gemm_row_split", 0)
+    g.sk_mode = 1;                     // the balanced tier is compiled into the lab build only (gemm_bf16.hip): the product lends no scratch
+#ifdef FP_LAB
     if (int rc = sk_scratch(g, s)) return rc;
+#endif
     return fp_gemm_bf16(g, epi, s);
 }
 size_t fp_ctx::total() const {
@@ -531,7 +532,7 @@ extern "C" int fp_op_gemm_patch(fp_ctx* ctx, const void* X, int ldx, const void*
 // route 0: fp_stats_finalize, then the consumer reads finished row records.  route 1: the consumer launch carries the partial sums
 // (LnStats::attach with the sums pending) and fp_gemm_bf16 decides who finalises them — the small tiers' prologue, each part of a row
 // split, or the finalisation kernel in front of the big tier (the forward never hands the sums to a big-tier launch: LnStats::ready
-// finalises up front there; route 1 on such a shape pins the fallback in launch_epi, which is the same kernel with the same arguments
+// finalises up front there; route 1 on such a shape pins the plan's finalize_first, which is the same kernel with the same arguments
 // as route 0).  The row records (16 bytes each)
 // and rstd are poisoned with 0xFF bytes first and copied out afterwards: d_mfrag [M,4] u32, d_rstd [M] f32.
 extern "C" int fp_op_ln_chain(fp_ctx* ctx, const void* X1, int K1, const void* W1, const void* b1, const void* gamma, const void* resid,
@@ -600,6 +601,16 @@ extern "C" int fp_op_workspace_read(fp_ctx* ctx, const char* name, void* host, s
     FP_REQUIRE(it != ctx->bufs.end() && it->second.bytes >= bytes, "op_workspace_read: no workspace '%s' of at least %zu bytes", name, bytes);
     FP_HIP(hipDeviceSynchronize());
     FP_HIP(hipMemcpy(host, it->second.p, bytes, hipMemcpyDeviceToHost));
+    return FP_OK;
+}
+// The plan fp_ctx::gemm would execute for a launch of this shape on this device, with this context's gemm_row_split, in words
+// (gemm_plan.h plan_text): nothing is launched.  What the tests of the tile tiers hold their case tables to.
+extern "C" int fp_op_gemm_plan(fp_ctx* ctx, int M, int N, int K, int epi, int ldx, int ldw, int ln_part, char* out, size_t out_bytes) {
+    FP_REQUIRE(ctx && out && out_bytes > 0, "op_gemm_plan: null argument");
+    FP_REQUIRE(M > 0 && N > 0 && K > 0 && epi >= FP_EPI_BIAS && epi <= FP_EPI_LS_RES_STATS, "op_gemm_plan: M=%d N=%d K=%d epi=%d", M, N, K, epi);
+    const fp_plan::Plan plan = fp_gemm_plan({M, N, K, epi, ldx, ldw, ln_part != 0, ctx->opt_row_split == 0});
+    const int n = fp_plan::plan_text(plan, out, out_bytes);
+    FP_REQUIRE(n >= 0 && (size_t)n < out_bytes, "op_gemm_plan: the text needs %d bytes", n + 1);
     return FP_OK;
 }
 // y = bf16(gelu_erf(x)) elementwise with the direct fp32 expression — the DEFINITION the fc1 epilogue's table is filled from; the

@@ -3,34 +3,15 @@
 // W keeps the torch nn.Linear layout ([out,in]) so a DINOv2 state-dict tensor is used as-is.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
-enum FpGemmEpi {
-    FP_EPI_BIAS = 0,        // C = acc + bias                           (QK part of qkv)
-    FP_EPI_BIAS_GELU = 1,   // C = gelu_erf(acc + bias)                 (fc1)
-    FP_EPI_BIAS_LS_RES = 2, // C = resid + gamma * (acc + bias)         (attn.proj / fc2 + LayerScale + residual)
-    FP_EPI_PATCH = 3,       // C[tokrow(m)] = bf16(acc + bias) + pos[p] (patch-embed -> token buffer)
-    FP_EPI_VT = 4,          // Vt[b,h,d,t] = acc + bias                 (V part of qkv, stored transposed per head)
-    // ---- LayerNorm folded into the consuming GEMM:  LN(x) W^T + b  =  rstd (x W'^T - mean colsum(W')) + b'
-    // with W' = W diag(gamma_ln) (bf16), colsum over the bf16 W', b' = b + W beta_ln (fp32).  X is the RAW residual stream.
-    // The correction rides in the ACCUMULATOR INIT: acc0[m][n] = b'[n] sigma[m] - mean[m] cs[n] (sigma = 1/rstd), the K loop adds
-    // x W'^T on top in fp32, and the epilogue is one multiply by rstd[m] — no per-feature constants are live in the epilogue.
-    // acc0 is a rank-2 outer product and is formed ON THE MATRIX PIPE: one extra MFMA per accumulator block whose operands carry,
-    // in 6 of their 32 k-slots, the two-piece bf16 splits (hi + lo, 16 mantissa bits) of (b', cs) per feature and (sigma, -mean) per
-    // row:  b' sigma ~ b'h sh + b'h sl + b'l sh  (relative error 2^-16), likewise mean cs.  Vector-ALU work at a tile boundary costs
-    // four times its instruction count (the four waves of a SIMD do it in lock-step with the matrix pipe idle): the VALU form of this
-    // init was +4-5 % on the qk / V / fc1 launches (profiles/r03_ab.md).
-    FP_EPI_LN_BIAS = 5,     // C = rstd (acc - mean cs) + b'            (QK part of qkv on the un-normalised x)
-    FP_EPI_LN_GELU = 6,     // C = gelu_erf(bf16(rstd (acc - mean cs) + b'))   (fc1)
-    FP_EPI_LN_VT = 7,       // Vt[b,h,d,t] = rstd (acc - mean cs) + b'  (V part of qkv)
-    // ---- the producer side: LS_RES that also writes, per row and 64-column block, (sum x, sum x^2) of its bf16 OUTPUT rows
-    FP_EPI_LS_RES_STATS = 8 // C = resid + gamma * (acc + bias);  stat_part[n/64][m] = (sum, sum of squares) over the block
-};
+// enum FpGemmEpi (the epilogues) lives in gemm_plan.h, beside the dispatch policy that reads it
 
 template <int EPI>
 struct FpEpiTraits {
-    static constexpr bool LN = EPI == FP_EPI_LN_BIAS || EPI == FP_EPI_LN_GELU || EPI == FP_EPI_LN_VT;
-    static constexpr bool TRANS = EPI == FP_EPI_VT || EPI == FP_EPI_LN_VT;
-    static constexpr bool GELU = EPI == FP_EPI_BIAS_GELU || EPI == FP_EPI_LN_GELU;
+    static constexpr bool LN = fp_plan::epi_ln(EPI);
+    static constexpr bool TRANS = fp_plan::epi_trans(EPI);
+    static constexpr bool GELU = fp_plan::epi_gelu(EPI);
     static constexpr bool LSRES = EPI == FP_EPI_BIAS_LS_RES || EPI == FP_EPI_LS_RES_STATS;
     static constexpr bool STATS = EPI == FP_EPI_LS_RES_STATS;
 };
@@ -151,16 +132,19 @@ __device__ __forceinline__ void fp_gemm_tile(int block, int nblocks, int tiles_m
 int fp_gemm_bf16(const FpGemmArgs& a, int epi, hipStream_t stream);
 // true when a row-major LN-folded launch of this size stays on the small tile tiers, i.e. finalises FpGemmArgs::ln_part in its prologue
 // (otherwise fp_gemm_bf16 runs fp_stats_finalize first; callers that account for that kernel separately call it themselves)
-bool fp_gemm_fuses_ln_part(int M, int N);
+inline bool fp_gemm_fuses_ln_part(int M, int N) { return fp_plan::fuses_ln_part(M, N); }
+// the device's CU count, queried once per process: the one source of `ncu` for the dispatch policy (gemm_plan.h ncu_*)
+int fp_gemm_device_cus();
+// the plan fp_gemm_bf16 executes for a launch of this shape on this device (gemm_plan.h; the lab build: under the lab options in force)
+fp_plan::Plan fp_gemm_plan(const fp_plan::Shape& s);
 // builds (once per device) and returns the bf16 -> bf16 GELU table the fc1 epilogue gathers from
 int fp_gemm_gelu_table(const uint16_t** out);
-// the hand-scheduled 256x256 kernel (gemm_asm.hip): the big-tile tier of the row-major epilogues
-bool fp_gemm_asm_supported(const FpGemmArgs& a, int epi);
-bool fp_gemm_asm_preferred(const FpGemmArgs& a, int epi);   // supported AND measured faster than the 16-wave kernel
+// the hand-scheduled 256x256 kernel (gemm_asm.hip): the big-tile tier of the row-major epilogues where fp_plan::asm_preferred holds
 int fp_gemm_asm(const FpGemmArgs& a, int epi, int waves, hipStream_t stream);   // waves: 4 (one per SIMD) or 8 (two per SIMD)
-// the hand-scheduled 128x128 kernel (gemm_asm.hip, geometry "S"): the small tier of the row-major epilogues
-bool fp_gemm_asm_small_supported(const FpGemmArgs& a, int epi);
+#ifdef FP_LAB
+// the hand-scheduled 128x128 kernel (gemm_asm.hip, geometry "S"): the small tier of the row-major epilogues, lab build only
 int fp_gemm_asm_small(const FpGemmArgs& a, int epi, hipStream_t stream);
+#endif
 // y[i] = bf16(gelu_erf(x[i])): the direct expression, elementwise (test entry fp_op_gelu)
 int fp_gemm_gelu_direct(const bf16_t* x, bf16_t* y, size_t n, hipStream_t stream);
 // name of the kernel variant used for (epi) — for profiles / bench bookkeeping

@@ -30,15 +30,18 @@
 #endif
 #define FP_GEMM_DEFAULT_VARIANT 238   // 2|4|8|32|64|128 (profiles/r02_ab.md: +4..6 % over 110 on every ViT shape)
 #define FP_GEMM_VAR_BIG (4 | 32 | 64 | 128)   // 16-wave 256x256: table GELU, persistent walk, streaming epilogue I/O, split DMA issue
-#define FP_GEMM_STREAM_BYTES (128L << 20)     // big-tier outputs above this are stored non-temporally (launch_epi: streaming policy)
 #define FP_GEMM_VAR_SMALL 6                   // 128x128 (4 waves): pipelined fragment reads, table GELU
 #define FP_GEMM_VAR_TINY (6 | 1024)           // 64x64 (2 waves, 1 for the transposed store): the same on a K-tile ring of run-time depth
+// kernel variant bits (template parameter VAR): 1 = s_setprio around MFMA blocks, 2 = software-pipelined fragment reads (8-wave
+// and smaller kernels), 4 = table GELU in the fc1 epilogue (gemm_epilogue.h; 0 = direct erff expression), 8 = 16-wave big tile,
+// 32 = persistent tile walk, 64 = streaming epilogue I/O: non-temporal output stores and residual loads (the last two with the
+// 16-wave big tile), 128 = split DMA issue (X pieces behind the first fragment reads, W pieces behind the first MFMA block) +
+// MFMA priority (persistent 16-wave kernel).  The product always runs FP_GEMM_DEFAULT_VARIANT; only the lab build can change it.
 
 namespace {
 
-constexpr int BK = 64;         // bf16 per K stage  (128-byte LDS rows)
-constexpr long BIG_MIN_TILES = 192;   // fewer 256x256 tiles than this never run on the big tier (launch_epi, fp_gemm_fuses_ln_part)
-constexpr int ROWB = BK * 2;   // bytes per LDS row
+constexpr int BK = fp_plan::BK;   // bf16 per K stage  (128-byte LDS rows)
+constexpr int ROWB = BK * 2;      // bytes per LDS row
 
 __device__ __forceinline__ int key_plain(int row) { return (row >> 1) & 7; }
 template <int T>
@@ -632,276 +635,221 @@ __global__ void gelu_direct_kernel(const bf16_t* x, bf16_t* y, size_t n) {
     if (i < n) y[i] = (bf16_t)(__float_as_uint(rbf(fp_gemm::gelu_erf(__uint_as_float((uint32_t)x[i] << 16)))) >> 16);
 }
 
+// Launches ONE kernel: `grid` workgroups, `ring` K-tile buffers where the kernel has a ring of run-time depth.  Which kernel, how many
+// workgroups and how deep a ring is the plan's business (gemm_plan.h); here the kernel's constants are held to the ones the plan budgets with.
 template <int BM, int BN, int WM, int WN, int EPI, int VAR>
-int launch_cfg(const FpGemmArgs& a, hipStream_t stream, int sk_grid = 0) {
+int launch_cfg(const FpGemmArgs& a, hipStream_t stream, int ring, int grid) {
     constexpr int STAGE = (BM + BN) * ROWB;
-    constexpr bool SK = (VAR & 2048) != 0;                   // balanced tier: sk_grid workgroups share the (tile, K step) units
+    constexpr bool SK = (VAR & 2048) != 0;                   // balanced tier: `grid` workgroups share the (tile, K step) units
     constexpr bool LUT = FpEpiTraits<EPI>::GELU && (VAR & 4) != 0;
     constexpr bool RING = (VAR & 2) && (VAR & 1024);
     constexpr int TABB = LUT ? fp_gemm::GELU_TAB_BYTES : 0;
     constexpr int SLABS = LUT ? 0 : WM * WN * fp_gemm::EPI_STAGE_BYTES;
-    constexpr int RMAX = RING ? ((160 * 1024 - TABB - SLABS - 16) / STAGE < 8 ? (160 * 1024 - TABB - SLABS - 16) / STAGE : 8) : 2;   // deepest ring that fits
+    constexpr int RMAX = RING ? fp_plan::ring_max(BM, BN, WM * WN, LUT) : 2;   // deepest ring that fits
+    static_assert(STAGE == fp_plan::stage_bytes(BM, BN) && TABB + SLABS == fp_plan::fixed_bytes(WM * WN, LUT) &&
+                      (BM + BN) / 8 / (WM * WN) == fp_plan::dma_per_stage(BM, BN, WM * WN), "gemm_plan.h budgets another kernel");
     constexpr int SMEM_MAX = TABB + RMAX * STAGE + (SK ? 16 : 0);   // dynamic part; the slabs are static (see the kernel)
-    static_assert(SMEM_MAX + SLABS <= 160 * 1024, "LDS budget");
+    static_assert(SMEM_MAX + SLABS <= fp_plan::LDS_BUDGET, "LDS budget");
     auto kern = gemm_bf16_kernel<BM, BN, WM, WN, EPI, VAR>;
     FP_DYN_LDS_ONCE(kern, SMEM_MAX);
-    int tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
     if constexpr (SK) {
-        FP_REQUIRE(sk_grid > 0 && sk_grid <= tiles * (a.K / BK) && a.sk_ws && a.sk_cnt && tiles <= a.sk_cnt_n &&
-                       (size_t)sk_grid * 2 * BM * BN * 4 <= a.sk_ws_bytes, "gemm: balanced tier without scratch (grid %d, %d tiles)", sk_grid, tiles);
-        tiles = sk_grid;
+        const int tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
+        FP_REQUIRE(grid > 0 && grid <= tiles * (a.K / BK) && a.sk_ws && a.sk_cnt && tiles <= a.sk_cnt_n &&
+                       (size_t)grid * 2 * BM * BN * 4 <= a.sk_ws_bytes, "gemm: balanced tier without scratch (grid %d, %d tiles)", grid, tiles);
     }
     FpGemmArgs ar = a;
-    ar.ring = 2;
-    if constexpr (RING) {
-        // the deepest ring (4 / 3 / 2 K-tile buffers) with which the whole grid is still resident at once; no deeper than K.  Deeper
-        // rings were measured and bring nothing (profiles/r04_ab.md §3: caps 8 / 6 / 4 / 3 within 1 %, 2 buffers 20-28 % slower at B = 1)
-        static int ncu_r = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-        constexpr int IPS = (BM + BN) / 8 / (WM * WN);
-        constexpr int FIXED = TABB + (LUT ? 0 : WM * WN * fp_gemm::EPI_STAGE_BYTES);
-        const int nkt = a.K / BK;
-        int cap = 4;
-#ifdef FP_LAB
-        cap = fp_opt_get(FP_OPT_GEMM_RING, 4);   // lab: up to 8
-#endif
-        for (const int r : {8, 6, 4, 3}) {
-            if ((r - 1) * IPS > 63 || r > nkt || r > cap || r > RMAX) continue;
-            const long resident = (long)ncu_r * ((160 * 1024) / (FIXED + r * STAGE));
-            if (tiles <= resident) { ar.ring = r; break; }
-        }
-    }
+    ar.ring = RING ? ring : 2;
+    FP_REQUIRE(grid > 0 && ar.ring >= 2 && ar.ring <= RMAX, "gemm: plan outside the kernel's limits (grid %d, ring %d)", grid, ar.ring);
     const int SMEM = TABB + ar.ring * STAGE + (SK ? 16 : 0);
-    if constexpr ((VAR & 32) != 0) {   // one resident workgroup per CU (128 KiB of LDS each)
-        static int ncu = [] { int dev = 0, n = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n & ~7; }();
-        tiles = tiles < ncu ? tiles : ncu;
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(WM * WN * 64), SMEM, stream, ar);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), SMEM, stream, ar);
     FP_LAUNCH_CHECK();
     return FP_OK;
 }
 
-template <int EPI>
-int launch_epi(const FpGemmArgs& a, hipStream_t stream) {
-    // big tile once the grid can fill the chip with it, else the 128x128 tile
-    const long tiles_big = (long)cdiv(a.M, 256) * cdiv(a.N, 256);
-    // kernel variant bits (template parameter VAR): 1 = s_setprio around MFMA blocks, 2 = software-pipelined fragment reads (8-wave
-    // and smaller kernels), 4 = table GELU in the fc1 epilogue (gemm_epilogue.h; 0 = direct erff expression), 8 = 16-wave big tile,
-    // 32 = persistent tile walk, 64 = streaming epilogue I/O: non-temporal output stores and residual loads (the last two with the
-    // 16-wave big tile), 128 = split DMA issue (X pieces behind the first fragment reads, W pieces behind the first MFMA block) +
-    // MFMA priority (persistent 16-wave kernel).  The product always runs FP_GEMM_DEFAULT_VARIANT; only the lab build can change it.
 #ifdef FP_LAB
+// ---- LAB BUILD ONLY: the options the plan is made under, and launches of kernels the plan does not know
+int lab_variant() {
     static int env_var = [] { const char* e = getenv("FP_GEMM_VARIANT"); return e ? atoi(e) : FP_GEMM_DEFAULT_VARIANT; }();
-    const int var = fp_opt_get(FP_OPT_GEMM_VARIANT, env_var);
-#else
-    constexpr int var = FP_GEMM_DEFAULT_VARIANT;
+    return fp_opt_get(FP_OPT_GEMM_VARIANT, env_var);
+}
+// gemm_variant bits that change the plan (A/B only): 256 = force the 128x128 kernel, 2048 = keep it below one tile per CU, 4096 = never
+// split, 8192 / 16384 = the hand-scheduled big kernel never / wherever it supports the shape, 32768 = one-wave tiles whenever not big,
+// 1048576 = the hand-scheduled 128x128 kernel as the small tier (with it 2097152 = only where the launch gives every CU a 128x128 tile,
+// 4194304 = only for K >= 2048), 8388608 = never stream; gemm_stream_mb = the streaming threshold in MiB (0 = always stream),
+// gemm_ring = cap on the 64x64 tier's ring (up to 8)
+fp_plan::Options lab_options() {
+    const int var = lab_variant();
+    fp_plan::Options o;
+    o.force_small = var & 256;
+    o.never_split = var & 4096;
+    o.keep_small = var & 2048;
+    o.tiny_unless_big = var & 32768;
+    o.asm_never = var & 8192;
+    o.asm_always = var & 16384;
+    o.asm_ln = true;
+    o.asm_small = var & 1048576;
+    o.asm_small_filled = var & 2097152;
+    o.asm_small_long_k = var & 4194304;
+    o.stream_bytes = (var & 8388608) ? 1L << 60 : (long)fp_opt_get(FP_OPT_GEMM_STREAM_MB, (int)(fp_plan::FP_GEMM_STREAM_BYTES >> 20)) << 20;
+    o.ring_cap = fp_opt_get(FP_OPT_GEMM_RING, fp_plan::RING_CAP);
+    return o;
+}
+// an alternative kernel for a tier the plan chose (sk_grid > 0: on the balanced tier's grid): its grid and ring by the plan's rules
+template <int BM, int BN, int WM, int WN, int EPI, int VAR>
+int launch_alt(const FpGemmArgs& a, hipStream_t stream, int sk_grid = 0) {
+    constexpr bool LUT = FpEpiTraits<EPI>::GELU && (VAR & 4) != 0;
+    const int n = fp_gemm_device_cus();
+    long grid = (VAR & 2048) ? sk_grid : (long)cdiv(a.M, BM) * cdiv(a.N, BN);
+    const int ring = fp_plan::ring_depth(grid, a.K / BK, BM, BN, WM * WN, LUT, fp_plan::ncu_resident(n), lab_options().ring_cap);
+    if (VAR & 32) grid = fp_plan::resident_grid(grid, fp_plan::ncu_persistent(n), fp_plan::LDS_BUDGET);
+    return launch_cfg<BM, BN, WM, WN, EPI, VAR>(a, stream, ring, (int)grid);
+}
 #endif
-    // The 256x256 kernels run one resident workgroup per CU, so their time goes in whole rounds of `ncu` tiles.  When the last
-    // round would be mostly empty (e.g. 300 tiles on 256 CUs: the ~20-crop batches of the video path) the 128x128 kernel —
-    // ~15-20 % less efficient per flop but 8x finer grained — is faster: measured 0.053 vs 0.068 ms (proj), 0.157 vs 0.192
-    // (fc2), 0.046 vs 0.063 (V) at M = 19 152, while the big tile wins whenever >= ~75 % of its rounds are filled.
-    static int ncu = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 8 ? (n & ~7) : 256; }();
-    const long rounds_big = (tiles_big + ncu - 1) / ncu;
-    if constexpr (FpEpiTraits<EPI>::LN) {
-        // row statistics handed over as partial sums: the small tiers finalise them in the kernel prologue; anything that may touch the
-        // big tier (or is a transposed store) gets them from the finalisation kernel first
-        if (a.ln_part && (FpEpiTraits<EPI>::TRANS || !fp_gemm_fuses_ln_part(a.M, a.N))) {
-            FP_REQUIRE(a.ln_part_nb > 0 && a.ln_part_ld >= a.M, "gemm: ln_part needs ln_part_nb and ln_part_ld");
-            const int rc = fp_stats_finalize(a.ln_part, a.ln_mfrag, a.ln_rstd, a.M, a.ln_part_nb * 64,
-                                             a.ln_eps, stream, a.ln_part_ld);
-            if (rc != FP_OK) return rc;
-            FpGemmArgs b = a;
-            b.ln_part = nullptr;
-            return launch_epi<EPI>(b, stream);
-        }
-    }
-    const bool filled = tiles_big * 4 >= rounds_big * ncu * 3;          // >= 75 % of the big-tile rounds are real work
-    bool big = tiles_big >= BIG_MIN_TILES && filled && !(var & 256);    // bit 256 (A/B only): force the 128x128 kernel
-    // (fp_gemm_fuses_ln_part shares BIG_MIN_TILES: a launch that still carries partial sums was promised the small tiers, which finalise
-    //  them in their prologue — the 256x256 kernels would read stale records)
+
+fp_plan::Shape shape_of(const FpGemmArgs& a, int epi) { return {a.M, a.N, a.K, epi, a.ldx, a.ldw, a.ln_part != nullptr, a.no_split != 0}; }
+
+// The arguments of one part of a launch, rows [p.row0, p.row0 + p.rows): the one place a row offset is applied
+FpGemmArgs part_args(const FpGemmArgs& a, const fp_plan::Part& p) {
+    FpGemmArgs b = a;
+    const size_t r = (size_t)p.row0;
+    b.M = p.rows;
+    if (p.rows < a.M) b.no_split = 1;          // a part of a split is never split again
+    if (b.stat_ld == 0) b.stat_ld = a.M;       // stat_part keeps the whole problem's row stride
+    b.X = a.X + r * a.ldx;
+    b.C = a.C + r * a.ldc;
+    if (a.resid) b.resid = a.resid + r * a.ldr;
+    if (a.ln_mfrag) b.ln_mfrag = a.ln_mfrag + r;
+    if (a.ln_rstd) b.ln_rstd = a.ln_rstd + r;
+    if (a.ln_part) b.ln_part = a.ln_part + r;
+    if (a.stat_part) b.stat_part = a.stat_part + r;
+    return b;
+}
+
+// One part of the plan on the tier it names: one kernel per (epilogue, tile tier).  The lab build's alternatives for a tier sit in one
+// block in front of it.
+template <int EPI>
+int launch_part(const FpGemmArgs& a, const fp_plan::Part& p, hipStream_t stream) {
+    constexpr bool TRANS = FpEpiTraits<EPI>::TRANS;
+    const bool big = p.tier >= fp_plan::BIG_HIP;
+    // (fuses_ln_part shares BIG_MIN_TILES: a launch that still carries partial sums was promised the small tiers, which finalise them in
+    //  their prologue — the 256x256 kernels would read stale records)
     FP_REQUIRE(!(big && a.ln_part), "gemm: partial row statistics on the big tier (M=%d N=%d)", a.M, a.N);
-    // The hand-scheduled 128x128 kernel (gemm_asm.hip, geometry "S": a persistent walk over two resident workgroups per CU, so no second
-    // row split below) as the small tier of the row-major epilogues: LAB BUILD ONLY — +8 ... 30 % on isolated launches with a resident X,
-    // -4 ... +17 % on ViT forwards (profiles/r05_ab.md §3), not shipped.  gemm_variant bit 1048576 = on; with it bit 2097152 = only where
-    // the launch gives every CU a 128x128 tile, bit 4194304 = only for K >= 2048.
-    bool asm_small = false;
 #ifdef FP_LAB
-    asm_small = !FpEpiTraits<EPI>::TRANS && (var & 1048576) && fp_gemm_asm_small_supported(a, EPI);
-    if ((var & 2097152) && (long)cdiv(a.M, 128) * cdiv(a.N, 128) < ncu) asm_small = false;
-    if ((var & 4194304) && a.K < 2048) asm_small = false;
-#endif
-    // ROW SPLIT (round 3): whole rounds of the resident grid on 256x256 tiles, the remaining rows on the finer tiers — for the launch
-    // sizes in between (the video path's ~20-crop batches: 600 qk tiles = 2.34 rounds, 300 proj / fc2 tiles = 1.17) where the big
-    // tile wastes most of a round and the small tile, ~0.56 of a big round per round of 2 tiles per CU at half the work, pays its
-    // lower efficiency on every row.  Rows are independent and every tier produces the same bits (tests/test_gpu_fullsize.py), so
-    // the split is invisible in the results.  Cost model in units of one big round; the split must win by 4 %.  Not for the
-    // transposed-V and patch-embed epilogues (their row -> output mapping is per crop).  Bit 4096 (A/B only): never split.
-    if constexpr (EPI != FP_EPI_VT && EPI != FP_EPI_LN_VT && EPI != FP_EPI_PATCH) {
-        const long tiles_n = cdiv(a.N, 256);
-        const long full = tiles_big / ncu;                               // whole rounds
-        const long rb = full * ncu / tiles_n;                            // 256-row blocks they cover
-        if (!(var & (256 | 4096)) && !a.no_split && full >= 1 && rb * 256 < a.M && tiles_big >= BIG_MIN_TILES) {
-            const double r_small = asm_small ? 0.45 : 0.56;   // a round of two 128x128 tiles per CU in units of a big round (half its work)
-            auto small_cost = [&](long rows) { return (double)cdiv(cdiv(rows, 128) * cdiv((long)a.N, 128), 2L * ncu) * r_small; };
-            const double t_big = (double)rounds_big, t_small = small_cost(a.M);
-            const double t_now = big ? t_big : t_small;
-            const double t_split = (double)cdiv(rb * tiles_n, (long)ncu) + small_cost(a.M - rb * 256);
-            if (t_split < 0.96 * t_now) {
-                const size_t m1 = (size_t)rb * 256;
-                FpGemmArgs a1 = a, a2 = a;
-                a1.M = (int)m1; a1.no_split = 1;
-                a2.M = a.M - (int)m1; a2.no_split = 1;
-                a2.X = a.X + m1 * a.ldx;
-                a2.C = a.C + m1 * a.ldc;
-                if (a.resid) a2.resid = a.resid + m1 * a.ldr;
-                if (a.ln_mfrag) a2.ln_mfrag = a.ln_mfrag + m1;
-                if (a.ln_rstd) a2.ln_rstd = a.ln_rstd + m1;
-                if (a.ln_part) a2.ln_part = a.ln_part + m1;
-                if (a.stat_part) a2.stat_part = a.stat_part + m1;
-                const int rc = launch_epi<EPI>(a1, stream);              // whole rounds: takes the 256x256 tier below
-                if (rc != FP_OK) return rc;
-                return launch_epi<EPI>(a2, stream);                      // the remainder picks its own tier (128x128 or 64x64)
+    const int var = lab_variant();
+    constexpr bool PLAIN = EPI < FP_EPI_LN_BIAS;   // the plain epilogues have alternative kernels (A/B runs: gemm_variant & 7 = 0 the baseline, else 6)
+    constexpr int WM8 = TRANS ? 2 : 4, WN8 = TRANS ? 4 : 2;   // the 128x128 tier on 8 waves
+    if (!big) {
+        // BALANCED TIER (round 5, measured and not shipped, profiles/r05_ab.md §1): G workgroups share the launch's (tile, K step) units
+        // evenly (stream-K); a tile whose K range is spread over several workgroups is completed by the last of them to arrive, which adds
+        // the fp32 partial tiles in K order.  Forms: gemm_sk = 2 / 3 / 4 -> 128x128 / 64x64 / 128x128-on-a-ring units, gemm_sk_grid = G.
+        if constexpr (EPI != FP_EPI_PATCH) {
+            const int f = fp_opt_get(FP_OPT_GEMM_SK, 0), g = fp_opt_get(FP_OPT_GEMM_SK_GRID, 0);
+            if (f >= 2 && f <= 4 && a.sk_ws && a.sk_cnt && a.sk_mode != 1) {
+                const int ncu = fp_plan::ncu_dispatch(fp_gemm_device_cus());
+                const long units = (long)cdiv(a.M, f == 3 ? 64 : 128) * cdiv(a.N, f == 3 ? 64 : 128) * (a.K / BK);
+                int sk_grid = (int)std::min<long>(units, g > 0 ? g : (f == 3 ? 4L : f == 4 ? 1L : 2L) * ncu);
+                sk_grid = (int)std::min<long>(sk_grid, (long)(a.sk_ws_bytes / (f == 3 ? 2 * 64 * 64 * 4 : 2 * 128 * 128 * 4)));
+                if (f == 2) return launch_alt<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL | 2048>(a, stream, sk_grid);
+                if (f == 3) return launch_alt<64, 64, fp_plan::tiny_waves(EPI), 1, EPI, FP_GEMM_VAR_TINY | 2048>(a, stream, sk_grid);
+                return launch_alt<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL | 1024 | 2048>(a, stream, sk_grid);
             }
         }
+        // the hand-scheduled 128x128 kernel in place of both small tiers (Options::asm_small)
+        if constexpr (!TRANS) {
+            if (fp_plan::asm_small_used(shape_of(a, EPI), a.M, fp_plan::ncu_dispatch(fp_gemm_device_cus()), lab_options())) return fp_gemm_asm_small(a, EPI, stream);
+        }
     }
-    // ROW SPLIT below the big tier (round 4): the 128x128 kernel keeps two workgroups per CU resident, so its time also goes in whole
-    // rounds (2 x ncu tiles) — 6 crops @518^2 give the N = 1024 layers 520 tiles = one round + 8 tiles, i.e. TWO rounds (the B = 5 -> 6
-    // step of a ViT-L forward was 6.1 -> 8.7 ms).  Whole rounds run on 128x128 tiles, the remaining rows pick their own tier (a
-    // remainder below one tile per CU takes the one-wave 64x64 tiles, whose round is ~half the cost).  Same bits from every tier.
-    if constexpr (EPI != FP_EPI_VT && EPI != FP_EPI_LN_VT && EPI != FP_EPI_PATCH) {
-        const long tn = cdiv(a.N, 128), slots = 2L * ncu, tiles_mid_all = (long)cdiv(a.M, 128) * tn;
-        const long fullm = tiles_mid_all / slots;
-        const long rbm = fullm * slots / tn;                              // 128-row blocks the whole rounds cover
-        if (!big && !asm_small && !(var & (256 | 4096)) && !a.no_split && fullm >= 1 && rbm * 128 < a.M) {
-            const long rem_rows = a.M - rbm * 128, rem_mid = cdiv(rem_rows, 128L) * tn;
-            const double t_now = (double)cdiv(tiles_mid_all, slots);
-            const double t_rem = rem_mid < ncu ? 0.5 * (double)cdiv(cdiv(rem_rows, 64L) * cdiv((long)a.N, 64L), 4L * ncu) : (double)cdiv(rem_mid, slots);
-            const double t_split = (double)cdiv(rbm * tn, slots) + t_rem;
-            if (t_split < 0.9 * t_now) {
-                const size_t m1 = (size_t)rbm * 128;
-                FpGemmArgs a1 = a, a2 = a;
-                a1.M = (int)m1; a1.no_split = 1;
-                a2.M = a.M - (int)m1; a2.no_split = 1;
-                a2.X = a.X + m1 * a.ldx;
-                a2.C = a.C + m1 * a.ldc;
-                if (a.resid) a2.resid = a.resid + m1 * a.ldr;
-                if (a.ln_mfrag) a2.ln_mfrag = a.ln_mfrag + m1;
-                if (a.ln_rstd) a2.ln_rstd = a.ln_rstd + m1;
-                if (a.ln_part) a2.ln_part = a.ln_part + m1;
-                if (a.stat_part) a2.stat_part = a.stat_part + m1;
-                const int rc = launch_epi<EPI>(a1, stream);
-                if (rc != FP_OK) return rc;
-                return launch_epi<EPI>(a2, stream);
+#endif
+    switch (p.tier) {
+        case fp_plan::TINY64:
+#ifdef FP_LAB
+            if constexpr (PLAIN) {
+                if (var != FP_GEMM_DEFAULT_VARIANT) return (var & 7) == 0 ? launch_alt<64, 64, 1, 1, EPI, 0>(a, stream) : launch_alt<64, 64, 1, 1, EPI, 6>(a, stream);
             }
-        }
-    }
-#ifdef FP_LAB
-    // BALANCED TIER (round 5, LAB BUILD ONLY — measured and not shipped, profiles/r05_ab.md §1): G workgroups share the launch's (tile, K
-    // step) units evenly (stream-K); a tile whose K range is spread over several workgroups is completed by the last of them to arrive,
-    // which adds the fp32 partial tiles in K order.  Forms: gemm_sk = 2 / 3 / 4 -> 128x128 / 64x64 / 128x128-on-a-ring units,
-    // gemm_sk_grid = G.
-    if constexpr (EPI != FP_EPI_PATCH) {
-        int sk_tier = 0, sk_grid = 0;
-        const int f = fp_opt_get(FP_OPT_GEMM_SK, 0), g = fp_opt_get(FP_OPT_GEMM_SK_GRID, 0);
-        if (f >= 2 && f <= 4 && !big && a.sk_ws && a.sk_cnt && a.sk_mode != 1) {
-            sk_tier = f - 1;
-            const long units = (long)cdiv(a.M, f == 3 ? 64 : 128) * cdiv(a.N, f == 3 ? 64 : 128) * (a.K / BK);
-            sk_grid = (int)std::min<long>(units, g > 0 ? g : (f == 3 ? 4L : f == 4 ? 1L : 2L) * ncu);
-            sk_grid = (int)std::min<long>(sk_grid, (long)(a.sk_ws_bytes / (f == 3 ? 2 * 64 * 64 * 4 : 2 * 128 * 128 * 4)));
-        }
-        if (sk_tier == 1) return launch_cfg<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL | 2048>(a, stream, sk_grid);
-        if (sk_tier == 2) {
-            if constexpr (FpEpiTraits<EPI>::TRANS) return launch_cfg<64, 64, 1, 1, EPI, FP_GEMM_VAR_TINY | 2048>(a, stream, sk_grid);
-            else return launch_cfg<64, 64, 2, 1, EPI, FP_GEMM_VAR_TINY | 2048>(a, stream, sk_grid);
-        }
-        if (sk_tier == 3) return launch_cfg<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL | 1024 | 2048>(a, stream, sk_grid);
-    }
+            if constexpr (!TRANS) {
+                if (var & 131072) return launch_alt<64, 64, 2, 1, EPI, FP_GEMM_VAR_SMALL>(a, stream);   // two K-tile buffers
+            }
+            if (var & 524288) return launch_alt<64, 64, fp_plan::tiny_waves(EPI), 1, EPI, FP_GEMM_VAR_TINY | 4096>(a, stream);   // spread DMA issue
 #endif
+            return launch_cfg<64, 64, fp_plan::tiny_waves(EPI), 1, EPI, FP_GEMM_VAR_TINY>(a, stream, p.ring, p.grid);
+        case fp_plan::SMALL128:
 #ifdef FP_LAB
-    if constexpr (!FpEpiTraits<EPI>::TRANS) {
-        if (!big && asm_small) return fp_gemm_asm_small(a, EPI, stream);
-    }
+            if constexpr (PLAIN) {
+                if (var != FP_GEMM_DEFAULT_VARIANT) return (var & 7) == 0 ? launch_alt<128, 128, 2, 2, EPI, 0>(a, stream) : launch_alt<128, 128, 2, 2, EPI, 6>(a, stream);
+            }
+            if (var & 524288)   // spread DMA issue
+                return (var & 262144) ? launch_alt<128, 128, WM8, WN8, EPI, FP_GEMM_VAR_SMALL | 4096>(a, stream) : launch_alt<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL | 4096>(a, stream);
+            if (var & 262144) return launch_alt<128, 128, WM8, WN8, EPI, FP_GEMM_VAR_SMALL>(a, stream);
 #endif
-    // A launch that cannot even give every CU one 128x128 tile (a single 518^2 crop: 88 tiles for N = 1024) runs one-wave
-    // 64x64 tiles instead — 4x the workgroups, all CUs busy (bit 2048, A/B only: keep the 128x128 kernel).
-    const long tiles_mid = (long)cdiv(a.M, 128) * cdiv(a.N, 128);
-    const bool tiny = !big && ((tiles_mid < ncu && !(var & 2048)) || (var & 32768));   // bit 32768 (lab A/B only): one-wave tiles whenever not big
-    // Big tier: the hand-scheduled one-wave-per-SIMD kernel (gemm_asm.hip) for the row-major
-    // epilogues where it is the faster one (fp_gemm_asm_preferred: long K), the 16-wave HIP kernel otherwise.
-    if constexpr (!FpEpiTraits<EPI>::TRANS) {
-        // lab A/B only: bit 8192 = never, bit 16384 = the 4-wave kernel wherever it supports the shape, bit 65536 = the 8-wave kernel
-        if (big && (var & 65536) && fp_gemm_asm_supported(a, EPI)) return fp_gemm_asm(a, EPI, 8, stream);
-        if (big && !(var & 8192) && ((var & 16384) ? fp_gemm_asm_supported(a, EPI) : fp_gemm_asm_preferred(a, EPI))) return fp_gemm_asm(a, EPI, 4, stream);
-    }
+            return launch_cfg<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL>(a, stream, p.ring, p.grid);
+        case fp_plan::BIG_ASM:
+            if constexpr (!TRANS) {
 #ifdef FP_LAB
-    if constexpr (EPI < FP_EPI_LN_BIAS) {   // lab build: the alternative kernels of the plain epilogues (A/B runs)
-        if (var != FP_GEMM_DEFAULT_VARIANT) {
-#define FP_GEMM_CASE(V)                                                          \
-    case V: return big ? launch_cfg<256, 256, 2, 4, EPI, V>(a, stream)          \
-               : tiny ? launch_cfg<64, 64, 1, 1, EPI, V>(a, stream)             \
-                      : launch_cfg<128, 128, 2, 2, EPI, V>(a, stream);
-            if (big && (var & 8)) {   // 16-wave workgroup (4 waves/SIMD), 64x64 per wave
-                switch (var & (32 | 64)) {   // 32: persistent tile walk, 64: streaming (non-temporal) output stores
-                    case 32: return launch_cfg<256, 256, 4, 4, EPI, 4 | 32>(a, stream);
-                    case 64: return launch_cfg<256, 256, 4, 4, EPI, 4 | 64>(a, stream);
-                    case 96:
-                        if ((var & 128) && (var & 512)) return launch_cfg<256, 256, 4, 4, EPI, 4 | 96 | 128 | 512>(a, stream);
-                        if ((var & 128) && (var & 1024)) return launch_cfg<256, 256, 4, 4, EPI, 4 | 96 | 128 | 1024>(a, stream);   // whole-N sweep of fc1 (round 6)
-                        return (var & 128) ? launch_cfg<256, 256, 4, 4, EPI, FP_GEMM_VAR_BIG>(a, stream)
-                                           : launch_cfg<256, 256, 4, 4, EPI, 4 | 96>(a, stream);
-                    default: return launch_cfg<256, 256, 4, 4, EPI, 4>(a, stream);
+                if (var & 65536) return fp_gemm_asm(a, EPI, 8, stream);   // the 8-wave geometry
+#endif
+                return fp_gemm_asm(a, EPI, 4, stream);
+            }
+            break;
+        case fp_plan::BIG_HIP:
+        case fp_plan::BIG_HIP_STREAM:
+#ifdef FP_LAB
+            if constexpr (!TRANS) {
+                if ((var & 65536) && fp_plan::asm_supported(shape_of(a, EPI), lab_options())) return fp_gemm_asm(a, EPI, 8, stream);
+            }
+            if constexpr (PLAIN) {
+                if (var != FP_GEMM_DEFAULT_VARIANT) {
+                    if (var & 8) {   // 16-wave workgroup (4 waves/SIMD), 64x64 per wave
+                        switch (var & (32 | 64)) {   // 32: persistent tile walk, 64: streaming (non-temporal) output stores
+                            case 32: return launch_alt<256, 256, 4, 4, EPI, 4 | 32>(a, stream);
+                            case 64: return launch_alt<256, 256, 4, 4, EPI, 4 | 64>(a, stream);
+                            case 96:
+                                if ((var & 128) && (var & 512)) return launch_alt<256, 256, 4, 4, EPI, 4 | 96 | 128 | 512>(a, stream);
+                                if ((var & 128) && (var & 1024)) return launch_alt<256, 256, 4, 4, EPI, 4 | 96 | 128 | 1024>(a, stream);   // whole-N sweep of fc1 (round 6)
+                                return (var & 128) ? launch_alt<256, 256, 4, 4, EPI, FP_GEMM_VAR_BIG>(a, stream) : launch_alt<256, 256, 4, 4, EPI, 4 | 96>(a, stream);
+                            default: return launch_alt<256, 256, 4, 4, EPI, 4>(a, stream);
+                        }
+                    }
+                    // measured on MI355X (profiles/): 6 is the fastest; 0 is kept as the plain baseline for A/B runs
+                    return (var & 7) == 0 ? launch_alt<256, 256, 2, 4, EPI, 0>(a, stream) : launch_alt<256, 256, 2, 4, EPI, 6>(a, stream);
                 }
             }
-            switch (var & 7) {   // measured on MI355X (profiles/): 6 is the fastest; 0 is kept as the plain baseline for A/B runs
-                FP_GEMM_CASE(0)
-                default:
-                FP_GEMM_CASE(6)
-            }
-#undef FP_GEMM_CASE
-        }
+#endif
+            // an output above the streaming threshold is stored non-temporally (gemm_plan.h: streaming policy)
+            return p.tier == fp_plan::BIG_HIP ? launch_cfg<256, 256, 4, 4, EPI, FP_GEMM_VAR_BIG & ~64>(a, stream, p.ring, p.grid)
+                                              : launch_cfg<256, 256, 4, 4, EPI, FP_GEMM_VAR_BIG>(a, stream, p.ring, p.grid);
     }
-#endif
-    // one kernel per (epilogue, tile tier)
-    // tiny tier: 64x64 tiles.  Row-major epilogues split the tile over TWO waves (32 x 64 each): a launch that cannot fill the chip is
-    // bound by one wave's walk along K, and per K step a lone wave issues 16 LDS-DMA pieces for 32 MFMAs — two waves halve both
-    // (ViT-L B = 1 @518^2: see profiles/r04_ab.md §4).  The transposed V store needs 64-token wave tiles and keeps one wave.
-    // STREAMING POLICY of the big tier (round 5).  Non-temporal full-line stores (and residual loads) keep a large output from dirtying
-    // every XCD's L2 (round 1: qk 0.373 -> 0.312 ms at 214 crops) — but an output that fits in the 256 MiB Infinity Cache beside its
-    // consumer's other operands is what the next kernel reads, and bypassing the caches sends that kernel to HBM.  Same-process A/B of
-    // ViT-L forwards with the threshold at 0 / 128 / 256 / 512 MiB / never, three boxes (profiles/r05_stream_policy_ab.log): ordinary
-    // stores below 128 MiB are 1.8-3.1 % faster at 5, 8 and 32 crops @420^2, -3 ... +1 % at 12 / 21 crops (box-dependent), neutral from
-    // 96 crops on; a 256 MiB threshold loses up to 1.5 % at 21-32 crops on two of the boxes; never streaming loses 1-3 % from 48 crops on.
-    long stream_bytes = FP_GEMM_STREAM_BYTES;
-#ifdef FP_LAB
-    stream_bytes = (long)fp_opt_get(FP_OPT_GEMM_STREAM_MB, (int)(FP_GEMM_STREAM_BYTES >> 20)) << 20;   // lab A/B: the threshold in MiB (0 = always stream)
-    if (var & 8388608) stream_bytes = 1L << 60;                                                          // bit 8388608: never stream
-#endif
-    const bool stream_out = (long)a.M * a.N * 2 > stream_bytes;
-    if (big && !stream_out) return launch_cfg<256, 256, 4, 4, EPI, FP_GEMM_VAR_BIG & ~64>(a, stream);
-    if constexpr (FpEpiTraits<EPI>::TRANS) {
-#ifdef FP_LAB
-        if (!big && !tiny && (var & 524288)) return (var & 262144) ? launch_cfg<128, 128, 2, 4, EPI, FP_GEMM_VAR_SMALL | 4096>(a, stream) : launch_cfg<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL | 4096>(a, stream);   // lab A/B: spread DMA issue
-        if (!big && tiny && (var & 524288)) return launch_cfg<64, 64, 1, 1, EPI, FP_GEMM_VAR_TINY | 4096>(a, stream);
-        if (!big && !tiny && (var & 262144)) return launch_cfg<128, 128, 2, 4, EPI, FP_GEMM_VAR_SMALL>(a, stream);   // lab A/B: 128x128 tier on 8 waves
-#endif
-        return big ? launch_cfg<256, 256, 4, 4, EPI, FP_GEMM_VAR_BIG>(a, stream)
-             : tiny ? launch_cfg<64, 64, 1, 1, EPI, FP_GEMM_VAR_TINY>(a, stream)
-                    : launch_cfg<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL>(a, stream);
-    } else {
-#ifdef FP_LAB
-        if (!big && tiny && (var & 131072)) return launch_cfg<64, 64, 2, 1, EPI, FP_GEMM_VAR_SMALL>(a, stream);   // lab A/B: two K-tile buffers
-        if (!big && !tiny && (var & 524288)) return (var & 262144) ? launch_cfg<128, 128, 4, 2, EPI, FP_GEMM_VAR_SMALL | 4096>(a, stream) : launch_cfg<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL | 4096>(a, stream);   // lab A/B: spread DMA issue
-        if (!big && tiny && (var & 524288)) return launch_cfg<64, 64, 2, 1, EPI, FP_GEMM_VAR_TINY | 4096>(a, stream);
-        if (!big && !tiny && (var & 262144)) return launch_cfg<128, 128, 4, 2, EPI, FP_GEMM_VAR_SMALL>(a, stream);   // lab A/B: 128x128 tier on 8 waves
-#endif
-        return big ? launch_cfg<256, 256, 4, 4, EPI, FP_GEMM_VAR_BIG>(a, stream)
-             : tiny ? launch_cfg<64, 64, 2, 1, EPI, FP_GEMM_VAR_TINY>(a, stream)
-                    : launch_cfg<128, 128, 2, 2, EPI, FP_GEMM_VAR_SMALL>(a, stream);
+    fp_set_error("gemm: tier %d has no kernel for epilogue %d", (int)p.tier, EPI);
+    return FP_ERR_INVALID;
+}
+
+int launch_epi(const FpGemmArgs& a, int epi, const fp_plan::Part& p, hipStream_t stream) {
+    switch (epi) {
+        case FP_EPI_BIAS: return launch_part<FP_EPI_BIAS>(a, p, stream);
+        case FP_EPI_BIAS_GELU: return launch_part<FP_EPI_BIAS_GELU>(a, p, stream);
+        case FP_EPI_BIAS_LS_RES: return launch_part<FP_EPI_BIAS_LS_RES>(a, p, stream);
+        case FP_EPI_PATCH: return launch_part<FP_EPI_PATCH>(a, p, stream);
+        case FP_EPI_VT: return launch_part<FP_EPI_VT>(a, p, stream);
+        case FP_EPI_LN_BIAS: return launch_part<FP_EPI_LN_BIAS>(a, p, stream);
+        case FP_EPI_LN_GELU: return launch_part<FP_EPI_LN_GELU>(a, p, stream);
+        case FP_EPI_LN_VT: return launch_part<FP_EPI_LN_VT>(a, p, stream);
+        default: return launch_part<FP_EPI_LS_RES_STATS>(a, p, stream);
     }
 }
 
 }  // namespace
 
-bool fp_gemm_fuses_ln_part(int M, int N) { return (long)cdiv(M, 256) * cdiv(N, 256) < BIG_MIN_TILES; }
+int fp_gemm_device_cus() {
+    static const int n = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
+    return n;
+}
+
+fp_plan::Plan fp_gemm_plan(const fp_plan::Shape& s) {
+#ifdef FP_LAB
+    return fp_plan::make_plan(s, fp_gemm_device_cus(), lab_options());
+#else
+    return fp_plan::make_plan(s, fp_gemm_device_cus());
+#endif
+}
 
 // Per-device GELU table (16 KiB), built on first use; fp_ctx_create calls this so that no launch path ever allocates.
 int fp_gemm_gelu_table(const uint16_t** out) {
@@ -929,7 +877,6 @@ int fp_gemm_bf16(const FpGemmArgs& a_in, int epi, hipStream_t stream) {
     static const int dbg_env = [] { const char* e = getenv("FP_GEMM_DBG"); return e ? atoi(e) : 0; }();
     a.dbg = fp_opt_get(FP_OPT_GEMM_DBG, dbg_env);
 #endif
-    if (a.stat_ld == 0) a.stat_ld = a.M;
     if (epi == FP_EPI_BIAS_GELU || epi == FP_EPI_LN_GELU) {
         const int rc = fp_gemm_gelu_table(&a.gelu_tab);
         if (rc != FP_OK) return rc;
@@ -941,33 +888,40 @@ int fp_gemm_bf16(const FpGemmArgs& a_in, int epi, hipStream_t stream) {
                "gemm: operand larger than 4 GiB (M=%d ldx=%d)", a.M, a.ldx);
     FP_REQUIRE((a.ldx % 8) == 0 && (a.ldw % 8) == 0 && (a.ldc % 8) == 0, "gemm: leading dims must be multiples of 8");
     switch (epi) {
-        case FP_EPI_BIAS: return launch_epi<FP_EPI_BIAS>(a, stream);
-        case FP_EPI_BIAS_GELU: return launch_epi<FP_EPI_BIAS_GELU>(a, stream);
-        case FP_EPI_BIAS_LS_RES:
-            FP_REQUIRE(a.gamma && a.resid, "gemm: LS_RES epilogue needs gamma and resid");
-            return launch_epi<FP_EPI_BIAS_LS_RES>(a, stream);
-        case FP_EPI_PATCH:
-            FP_REQUIRE(a.pos && a.P > 0 && a.npad > 0, "gemm: PATCH epilogue needs pos/P/npad");
-            return launch_epi<FP_EPI_PATCH>(a, stream);
-        case FP_EPI_VT:
-            FP_REQUIRE(a.npad % 16 == 0 && a.M % 16 == 0 && a.heads > 0 && a.N == a.heads * 64,
-                       "gemm: VT epilogue needs npad%%16==0, M%%16==0, N==heads*64");
-            return launch_epi<FP_EPI_VT>(a, stream);
+        case FP_EPI_BIAS:
+        case FP_EPI_BIAS_GELU: break;
+        case FP_EPI_BIAS_LS_RES: FP_REQUIRE(a.gamma && a.resid, "gemm: LS_RES epilogue needs gamma and resid"); break;
+        case FP_EPI_PATCH: FP_REQUIRE(a.pos && a.P > 0 && a.npad > 0, "gemm: PATCH epilogue needs pos/P/npad"); break;
         case FP_EPI_LN_BIAS:
         case FP_EPI_LN_GELU:
             FP_REQUIRE(a.ln_mfrag && a.ln_rstd && a.ln_cfrag && a.N % 64 == 0 && a.M >= 16,
                        "gemm: LN-folded epilogue needs ln_mfrag, ln_rstd, ln_cfrag, N %% 64 == 0 and M >= 16 (M=%d N=%d)", a.M, a.N);
-            return epi == FP_EPI_LN_BIAS ? launch_epi<FP_EPI_LN_BIAS>(a, stream) : launch_epi<FP_EPI_LN_GELU>(a, stream);
+            break;
         case FP_EPI_LN_VT:
             FP_REQUIRE(a.ln_mfrag && a.ln_rstd && a.ln_cfrag, "gemm: LN-folded epilogue needs ln_mfrag, ln_rstd and ln_cfrag");
+            [[fallthrough]];
+        case FP_EPI_VT:
             FP_REQUIRE(a.npad % 16 == 0 && a.M % 16 == 0 && a.heads > 0 && a.N == a.heads * 64,
                        "gemm: VT epilogue needs npad%%16==0, M%%16==0, N==heads*64");
-            return launch_epi<FP_EPI_LN_VT>(a, stream);
+            break;
         case FP_EPI_LS_RES_STATS:
             FP_REQUIRE(a.gamma && a.resid && a.stat_part && a.N % 64 == 0, "gemm: LS_RES_STATS epilogue needs gamma, resid, stat_part, N %% 64 == 0");
-            return launch_epi<FP_EPI_LS_RES_STATS>(a, stream);
+            break;
         default: fp_set_error("gemm: unknown epilogue %d", epi); return FP_ERR_INVALID;
     }
+    // plan, then launch: who finalises the row statistics, then each part on its tier
+    const fp_plan::Plan plan = fp_gemm_plan(shape_of(a, epi));
+    if (plan.finalize_first) {
+        FP_REQUIRE(a.ln_part_nb > 0 && a.ln_part_ld >= a.M, "gemm: ln_part needs ln_part_nb and ln_part_ld");
+        const int rc = fp_stats_finalize(a.ln_part, a.ln_mfrag, a.ln_rstd, a.M, a.ln_part_nb * 64, a.ln_eps, stream, a.ln_part_ld);
+        if (rc != FP_OK) return rc;
+        a.ln_part = nullptr;
+    }
+    for (int i = 0; i < plan.nparts; ++i) {
+        const int rc = launch_epi(part_args(a, plan.part[i]), epi, plan.part[i], stream);
+        if (rc != FP_OK) return rc;
+    }
+    return FP_OK;
 }
 
 int fp_gemm_gelu_direct(const bf16_t* x, bf16_t* y, size_t n, hipStream_t stream) {

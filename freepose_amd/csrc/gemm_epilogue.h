@@ -22,7 +22,8 @@ __device__ __forceinline__ float gelu_erf(float x) {
 // Index of pattern p (16 bit): (p & 0xfff) | ((p >> 3) & 0x1000): the low 5 exponent bits + mantissa are taken as they are (the
 // window 112 <= exp < 144 is a bijection onto exp & 31), the sign moves next to them.
 constexpr int GELU_TAB_ENTRIES = 8192;
-constexpr int GELU_TAB_BYTES = GELU_TAB_ENTRIES * 2;
+constexpr int GELU_TAB_BYTES = fp_plan::GELU_TAB_BYTES;   // (stated in gemm_plan.h: the launch policy budgets the LDS with it)
+static_assert(GELU_TAB_BYTES == GELU_TAB_ENTRIES * 2, "GELU table: one bf16 per entry");
 constexpr uint32_t GELU_WIN_LO = 112u << 7, GELU_WIN_HI = 144u << 7;      // abs-pattern window [LO, HI)
 
 __device__ __forceinline__ uint32_t gelu_tab_pattern(int i) {              // table index -> bf16 input pattern
@@ -145,7 +146,7 @@ __device__ __forceinline__ void gelu_tab16_finish(GeluPending& st, uint32_t (&ou
 }
 
 // bytes of LDS each wave needs for the row-coalescing stage of the non-transposed epilogues (16 rows x 128 B)
-constexpr int EPI_STAGE_BYTES = 2048;
+constexpr int EPI_STAGE_BYTES = fp_plan::EPI_STAGE_BYTES;
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 

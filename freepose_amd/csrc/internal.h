@@ -23,16 +23,20 @@ struct fp_ctx {
     int opt_raster_tiled = -1;   // default: by triangle count / image size; 1 / 0 force the LDS-tiled / global-buffer strategy
     int opt_comm_timeout_s = -1; // seconds fp_comm_init waits for the rendezvous of all ranks before it fails (default 180)
     int opt_row_split = -1;      // 1 (default): GEMM launches between the tile tiers are split by rows; 0: never
-    int opt_stream_k = -1;       // 1 (default): small GEMM launches may run on the balanced tier (K slices summed in K order: results depend
-                                 // on the launch size in the last place); 0: never — every tier then gives the same bits for a row
-    // scratch of the balanced GEMM tier (gemm_bf16.h FpGemmArgs::sk_*): fp32 partial tiles + zero-initialised arrival counters
+    // scratch of the balanced GEMM tier (gemm_bf16.h FpGemmArgs::sk_*): fp32 partial tiles + zero-initialised arrival counters.  The tier
+    // is compiled into the lab build only: the product never allocates these and every launch goes out with sk_mode = 1 (never), so every
+    // tier gives the same bits for a row
     float* sk_ws = nullptr;
     int* sk_cnt = nullptr;
     static constexpr size_t SK_WS_BYTES = (size_t)64 << 20;
     static constexpr int SK_CNT_N = 16384;
+#ifdef FP_LAB
+    int opt_stream_k = -1;       // lab option "gemm_stream_k": 0 = never lend the scratch; else launches below the big tier may run on the
+                                 // balanced tier when gemm_sk asks for it (K slices summed in K order: results depend on the launch size)
     int sk_scratch(FpGemmArgs& g, hipStream_t s);   // lends the scratch to a launch (allocates on first use)
-    // THE launch path of every bf16 GEMM of the library: applies the context's options (gemm_row_split -> no_split), lends the
-    // balanced tier its scratch and calls fp_gemm_bf16
+#endif
+    // THE launch path of every bf16 GEMM of the library: applies the context's options (gemm_row_split -> no_split), in the lab build lends
+    // the balanced tier its scratch, and calls fp_gemm_bf16
     int gemm(FpGemmArgs& g, int epi, hipStream_t s);
     int* ffa_arrive = nullptr;   // per-crop arrival counters of the fused FFA launch (zero between calls: the last arriver resets its own)
     size_t total() const;

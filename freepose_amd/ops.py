@@ -1139,6 +1139,23 @@ def ln_consume(x: torch.Tensor, rec: torch.Tensor, rstd: torch.Tensor, g_ln: tor
     return out
 
 
+def gemm_plan(M: int, N: int, K: int, epi: int, ldx: Optional[int] = None, ldw: Optional[int] = None, ln_part: bool = False,
+              device: Optional[int] = None) -> dict:
+    """the plan the library's GEMM dispatch would execute on this device for such a launch, under the context's gemm_row_split
+    (fp_op_gemm_plan; nothing is launched): {"label": tiny64 | small128 | big_hip | big_hip_stream | big_asm | split_big+<tier> |
+    split_mid+<tier> | finalize_then_<label>, "row0": first row of the second part (0 = no split), "ring": K-tile ring depth of each part
+    (0: not on the 64x64 tier), "grid": workgroups of each part, "text": the entry's own line}"""
+    import ctypes
+    buf = ctypes.create_string_buffer(160)
+    check(_lib.load().fp_op_gemm_plan(context(device), int(M), int(N), int(K), int(epi), int(K if ldx is None else ldx), int(K if ldw is None else ldw),
+                                      int(bool(ln_part)), buf, len(buf)), "fp_op_gemm_plan")
+    text = buf.value.decode()
+    label, *fields = text.split()
+    kv = dict(f.split("=") for f in fields)
+    return {"label": label, "row0": int(kv["row0"]), "ring": tuple(int(v) for v in kv["ring"].split(",")),
+            "grid": tuple(int(v) for v in kv["grid"].split(",")), "text": text}
+
+
 def workspace_read(name: str, shape, dtype=torch.bfloat16, device: Optional[int] = None) -> torch.Tensor:
     """the head of the context workspace `name` ("vit.x", "clip.qkv", ...: what the last tower forward left there) as a host tensor of
     `shape` and `dtype` (fp_op_workspace_read); raises when the context has no such workspace or it is shorter"""

@@ -323,6 +323,15 @@ int fp_op_ln_consume(fp_ctx* ctx, const void* d_X, int M, int K, const void* d_g
  * "clip.qkv", "clip_text.pool", ...) to host memory, after a device synchronisation; an unknown name or a workspace shorter than `bytes`
  * is an error.  Host-only entry used by the tests that replay a forward step by step. */
 int fp_op_workspace_read(fp_ctx* ctx, const char* name, void* host, size_t bytes);
+/* writes into `out` (at most out_bytes, NUL-terminated) the plan the GEMM dispatch of this context would execute on this device for a
+ * launch C[M,N] = epi(X[M,K] W[N,K]^T) — epi = the library's nine epilogues 0 .. 8, ldx / ldw the operands' row strides, ln_part != 0: the
+ * launch carries partial row statistics — under the context's "gemm_row_split"; launches nothing.  The text is
+ *   <label> row0=<r> ring=<a>,<b> grid=<a>,<b>
+ * with <label> one of tiny64 | small128 | big_hip | big_hip_stream | big_asm, split_big+<tier> / split_mid+<tier> (whole rounds on the
+ * 256x256 / 128x128 tiles in front, <tier> = where the remaining rows run), finalize_then_<label> (the row statistics are finalised by a
+ * kernel in front); row0 = the first row of the second part (0 = no split), ring = K-tile ring depth of each part (0: not on the 64x64
+ * tier), grid = workgroups of each part.  Host-only entry used by the tests of the tile tiers. */
+int fp_op_gemm_plan(fp_ctx* ctx, int M, int N, int K, int epi, int ldx, int ldw, int ln_part, char* out, size_t out_bytes);
 /* d_y[i] = bf16(0.5 x (1 + erf(x / sqrt 2))) elementwise on bf16 values in fp32: the direct expression the fc1 epilogue's GELU table
  * is filled from (hub DINOv2 Mlp act_layer = nn.GELU behind src/pipeline/retrieval/dino.py:18-19); the table-GELU GEMM is tested
  * against it on all 65 536 bf16 inputs */

@@ -29,9 +29,13 @@ def cdiv(a, b):
     return -(-a // b)
 
 
-# ---- dispatch mirror (gemm_bf16.hip launch_epi, product build) ---------------------------------------------------------------------------
+# ---- dispatch mirror (csrc/gemm_plan.h make_plan under the product's options).  A restatement written by hand, held to the header itself by
+# tests/test_gemm_cases_cpu.py (tools/gemm_plan_host_check.cpp on every case and a sweep of 10^5 shapes) and to the library on the device by
+# tests/test_gpu_gemm_branches.py (fp_op_gemm_plan).  The part in FRONT of a split picks its tier by the same rule as any launch: nearly
+# always the 256x256 / 128x128 tiles the split is named for, but e.g. 139 775 x 48 on 256 CUs — 546 big tiles, 2.13 rounds, not filled — takes
+# split_mid, whose front of 131 072 rows is 512 big tiles = two full rounds and runs on the big tier.
 def asm_preferred(K, epi, ldx, ldw):
-    """fp_gemm_asm_preferred: the hand-scheduled 256x256 kernel is instantiated for BIAS, GELU, LS_RES, LS_RES_STATS, takes K steps in pairs
+    """fp_plan::asm_preferred: the hand-scheduled 256x256 kernel is instantiated for BIAS, GELU, LS_RES, LS_RES_STATS, takes K steps in pairs
     and 128-byte aligned rows, and is the faster one from K = 2048 on"""
     supported = epi in (BIAS, GELU, LS_RES, LS_RES_STATS) and K % 128 == 0 and K >= 256 and ldx % 64 == 0 and ldw % 64 == 0
     return supported and K >= 2048
@@ -41,20 +45,38 @@ def fuses_ln_part(M, N):
     return cdiv(M, 256) * cdiv(N, 256) < BIG_MIN_TILES
 
 
-def branch(M, N, K, epi, n_cu=256, ldx=None, ldw=None, row_split=True, ln_part=False):
-    """label of the path fp_gemm_bf16 takes: tiny64 | small128 | big_hip | big_hip_stream | big_asm, split_big+<rest> / split_mid+<rest> (<rest>
-    = the path of the remaining rows; the whole rounds in front run on the big tier / on 128x128 tiles), finalize_then_<path> when a launch
-    that carries partial row statistics is finalised by the host-side kernel first"""
+def _ncu(n_cu):
+    return (n_cu & ~7) if n_cu > 8 else 256
+
+
+def _is_big(M, N, ncu):
+    tiles_big = cdiv(M, 256) * cdiv(N, 256)
+    return tiles_big >= BIG_MIN_TILES and tiles_big * 4 >= cdiv(tiles_big, ncu) * ncu * 3      # >= 75 % of the big-tile rounds are real work
+
+
+def _tier(M, N, K, epi, ncu, ldx, ldw):
+    """the tier of M rows launched unsplit"""
+    if _is_big(M, N, ncu):
+        if epi not in (VT, LN_VT) and asm_preferred(K, epi, ldx, ldw):
+            return "big_asm"
+        return "big_hip_stream" if M * N * 2 > STREAM_BYTES else "big_hip"
+    return "tiny64" if cdiv(M, 128) * cdiv(N, 128) < ncu else "small128"
+
+
+def plan(M, N, K, epi, n_cu=256, ldx=None, ldw=None, row_split=True, ln_part=False):
+    """(label, row0) of the path fp_gemm_bf16 takes.  label: tiny64 | small128 | big_hip | big_hip_stream | big_asm, split_big+<rest> /
+    split_mid+<rest> (<rest> = the tier of the remaining rows; the whole rounds in front run on 256x256 / on 128x128 tiles),
+    finalize_then_<path> when a launch that carries partial row statistics is finalised by the host-side kernel first.  row0: the rows in
+    front of the split (0 = none)"""
     ldx = K if ldx is None else ldx
     ldw = K if ldw is None else ldw
-    ncu = (n_cu & ~7) if n_cu > 8 else 256
+    ncu = _ncu(n_cu)
     trans, ln = epi in (VT, LN_VT), epi in (LN_BIAS, LN_GELU, LN_VT)
-    tiles_big = cdiv(M, 256) * cdiv(N, 256)
-    rounds_big = cdiv(tiles_big, ncu)
+    prefix = ""
     if ln and ln_part and (trans or not fuses_ln_part(M, N)):
-        return "finalize_then_" + branch(M, N, K, epi, n_cu, ldx, ldw, row_split, False)
-    filled = tiles_big * 4 >= rounds_big * ncu * 3
-    big = tiles_big >= BIG_MIN_TILES and filled
+        prefix, ln_part = "finalize_then_", False
+    tiles_big = cdiv(M, 256) * cdiv(N, 256)
+    big = _is_big(M, N, ncu)
     assert not (big and ln_part)
     if epi not in (VT, LN_VT, PATCH) and row_split:
         tiles_n = cdiv(N, 256)
@@ -63,12 +85,10 @@ def branch(M, N, K, epi, n_cu=256, ldx=None, ldw=None, row_split=True, ln_part=F
         if full >= 1 and rb * 256 < M and tiles_big >= BIG_MIN_TILES:
             def small_cost(rows):
                 return float(cdiv(cdiv(rows, 128) * cdiv(N, 128), 2 * ncu)) * 0.56
-            t_now = float(rounds_big) if big else small_cost(M)
+            t_now = float(cdiv(tiles_big, ncu)) if big else small_cost(M)
             t_split = float(cdiv(rb * tiles_n, ncu)) + small_cost(M - rb * 256)
             if t_split < 0.96 * t_now:
-                first = branch(rb * 256, N, K, epi, n_cu, ldx, ldw, False, ln_part)
-                assert first.startswith("big_"), first
-                return "split_big+" + branch(M - rb * 256, N, K, epi, n_cu, ldx, ldw, False, ln_part)
+                return prefix + "split_big+" + _tier(M - rb * 256, N, K, epi, ncu, ldx, ldw), rb * 256
         tn, slots = cdiv(N, 128), 2 * ncu
         tiles_mid_all = cdiv(M, 128) * tn
         fullm = tiles_mid_all // slots
@@ -80,27 +100,17 @@ def branch(M, N, K, epi, n_cu=256, ldx=None, ldw=None, row_split=True, ln_part=F
             t_rem = 0.5 * float(cdiv(cdiv(rem_rows, 64) * cdiv(N, 64), 4 * ncu)) if rem_mid < ncu else float(cdiv(rem_mid, slots))
             t_split = float(cdiv(rbm * tn, slots)) + t_rem
             if t_split < 0.9 * t_now:
-                first = branch(rbm * 128, N, K, epi, n_cu, ldx, ldw, False, ln_part)
-                assert first == "small128", first
-                return "split_mid+" + branch(rem_rows, N, K, epi, n_cu, ldx, ldw, False, ln_part)
-    tiles_mid = cdiv(M, 128) * cdiv(N, 128)
-    if big:
-        if not trans and asm_preferred(K, epi, ldx, ldw):
-            return "big_asm"
-        return "big_hip_stream" if M * N * 2 > STREAM_BYTES else "big_hip"
-    return "tiny64" if tiles_mid < ncu else "small128"
+                return prefix + "split_mid+" + _tier(rem_rows, N, K, epi, ncu, ldx, ldw), rbm * 128
+    return prefix + _tier(M, N, K, epi, ncu, ldx, ldw), 0
+
+
+def branch(M, N, K, epi, n_cu=256, ldx=None, ldw=None, row_split=True, ln_part=False):
+    return plan(M, N, K, epi, n_cu, ldx, ldw, row_split, ln_part)[0]
 
 
 def split_point(M, N, n_cu=256):
-    """rows in front of the row split a launch of this size takes (0 = none), for choosing the rows a subset check must contain"""
-    ncu = (n_cu & ~7) if n_cu > 8 else 256
-    tiles_big = cdiv(M, 256) * cdiv(N, 256)
-    rb = (tiles_big // ncu) * ncu // cdiv(N, 256)
-    if tiles_big >= BIG_MIN_TILES and tiles_big // ncu >= 1 and rb * 256 < M:
-        return rb * 256
-    tn = cdiv(N, 128)
-    rbm = (cdiv(M, 128) * tn // (2 * ncu)) * 2 * ncu // tn
-    return rbm * 128 if 0 < rbm * 128 < M else 0
+    """rows in front of the row split a row-major launch of this size takes (0 = none), for choosing the rows a subset check must contain"""
+    return plan(M, N, 64, BIAS, n_cu)[1]
 
 
 # ---- bf16 rounding -------------------------------------------------------------------------------------------------------------------
@@ -229,13 +239,13 @@ def pos_ints(case):
     return hash_ints(p, n, case.seed + 505, -127, 127)
 
 
-def check_rows(case, n_cu=256):
+def check_rows(case, n_cu=256, split_row=None):
     """all rows, or for `subset` cases: the first tile, the last two tiles (every ragged one), 256 rows on both sides of a row split and a
-    stride of 61 through the rest"""
+    stride of 61 through the rest.  split_row: where the library says it splits the launch (default: where the mirror says)"""
     if not case.subset:
         return np.arange(case.M, dtype=np.int64)
     pick = set(range(0, min(256, case.M))) | set(range(max(0, case.M - 512), case.M)) | set(range(0, case.M, 61))
-    sp = split_point(case.M, case.N, n_cu) if case.epi not in (VT, PATCH) else 0
+    sp = split_row if split_row is not None else split_point(case.M, case.N, n_cu) if case.epi not in (VT, PATCH) else 0
     if sp:
         pick |= set(range(max(0, sp - 256), min(case.M, sp + 256)))
     return np.array(sorted(pick), dtype=np.int64)
@@ -442,7 +452,7 @@ CHAINS = [
     Chain("chain_small_2090_m1", 2090, 256, 2048, 1, "small128", seed=806),                                       # ragged against 16, 64, 128
     Chain("chain_splitmid_8256_m0", 8256, 256, 1024, 0, "split_mid+tiny64", seed=807),
     Chain("chain_splitmid_8250_m1", 8250, 256, 1024, 1, "split_mid+tiny64", seed=808),                            # remainder ragged against 16, 64
-    # the two below: fp_vit_forward finalises such shapes itself and never sets ln_part on them; route 1 pins launch_epi's own fallback,
+    # the two below: fp_vit_forward finalises such shapes itself and never sets ln_part on them; route 1 pins the plan's finalize_first,
     # which runs the same finalisation kernel as route 0, so the routes agree by construction and only the bound and the records tell
     Chain("chain_finalize_49152_m0", 49152, 256, 256, 0, "finalize_then_big_hip", seed=809),
     Chain("chain_finalize_48897_m1", 48897, 256, 256, 1, "finalize_then_big_hip", seed=810),

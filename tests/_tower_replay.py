@@ -18,7 +18,7 @@ import torch
 
 LN_EPS_VIT = 1e-6
 LN_EPS_CLIP = 1e-5
-BIG_MIN_TILES = 192      # csrc/gemm_bf16.hip: fewer 256 x 256 tiles than this never run on the big tile tier
+BIG_MIN_TILES = 192      # csrc/gemm_plan.h: fewer 256 x 256 tiles than this never run on the big tile tier
 
 FAULTS_VIT = ("ls_swapped", "ls_ignored", "ln_eps_1e-5", "pos_shifted", "grid_transposed", "tok_off_no_registers", "ln1_records_stale",
               "last_block_sums_stale", "vt_records_from_rows", "q_scaled_twice")

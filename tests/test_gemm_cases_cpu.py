@@ -1,6 +1,10 @@
 """No-GPU proof obligations of tests/_gemm_cases.py: every case reaches the branch it claims on 256 CUs, the exact operands really are
 exact (every partial sum below 2^24 quanta, float32 and float64 evaluation of the rounding chains agree), the rounding points are exercised
 (values bf16 cannot represent, exact ties) and round_bf16_rne is torch's round-to-nearest-even on every bf16 neighbourhood."""
+import shutil
+import subprocess
+from pathlib import Path
+
 import numpy as np
 import pytest
 import torch
@@ -54,8 +58,141 @@ def test_chain_lands_in_the_branch_it_claims(ch):
     assert gc.branch(prod.M, prod.N, prod.K, prod.epi) in ("tiny64", "small128", "big_hip", "split_mid+tiny64")
 
 
+# ---- the library's own statement of the dispatch (csrc/gemm_plan.h) against the mirror -----------------------------------------------------
+ROOT = Path(__file__).resolve().parent.parent
+LN_EPIS = (gc.LN_BIAS, gc.LN_GELU, gc.LN_VT)
+
+
+@pytest.fixture(scope="module")
+def plan_check(tmp_path_factory):
+    """tools/gemm_plan_host_check.cpp under the host sanitizers: [(M, N, K, epi, ldx, ldw, ln_part, no_split, ncu)] -> [(label, row0, rings,
+    grids)], exit status 0 (its own checks of every plan and the sanitizers)"""
+    gxx = shutil.which("g++")
+    assert gxx, "g++ not found"
+    exe = tmp_path_factory.mktemp("gemm_plan") / "gemm_plan_host_check"
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", str(ROOT / "freepose_amd" / "csrc"),
+           str(ROOT / "tools" / "gemm_plan_host_check.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+    def run(shapes):
+        text = "".join(" ".join(str(int(v)) for v in s) + "\n" for s in shapes)
+        r = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+        out = []
+        for ln in r.stdout.splitlines():
+            label, row0, ring, grid = ln.split()
+            out.append((label, int(row0.split("=")[1]), tuple(int(v) for v in ring.split("=")[1].split(",")),
+                        tuple(int(v) for v in grid.split("=")[1].split(","))))
+        assert len(out) == len(shapes)
+        return out
+    return run
+
+
+def _mirror(shape):
+    M, N, K, epi, ldx, ldw, ln_part, no_split, ncu = shape
+    return gc.plan(M, N, K, epi, ncu, ldx, ldw, not no_split, bool(ln_part))
+
+
+def _assert_plans_equal_mirror(plan_check, shapes):
+    got = plan_check(shapes)
+    for s, g in zip(shapes, got):
+        label, row0 = _mirror(s)
+        assert (g[0], g[1]) == (label, row0), f"M N K epi ldx ldw ln_part no_split ncu = {s}: gemm_plan.h says {g[0]} row0={g[1]}, the mirror {label} row0={row0}"
+        if s[3] not in (gc.VT, gc.LN_VT, gc.PATCH) and not s[7]:
+            assert gc.split_point(s[0], s[1], s[8]) == g[1], s
+    return got
+
+
+def test_plan_of_every_committed_case_is_its_claim(plan_check):
+    """planner == mirror == the case's claim at 256 CUs, chains with the partial sums handed over; and the tiny cases that
+    tests/test_gpu_gemm_branches.py names "a K ring of depth 2 .. 4" really run on rings of 2, 3 and 4 buffers"""
+    cases = [(c.M, c.N, c.K, c.epi, c.ld("x"), c.ld("w"), 0, 0, 256) for c in gc.EXACT_CASES]
+    chains = [(c.M, c.N2, c.D, gc.LN_BIAS if c.mode == 0 else gc.LN_GELU, c.D, c.D, 1, 0, 256) for c in gc.CHAINS]
+    got = _assert_plans_equal_mirror(plan_check, cases + chains)
+    for c, g in zip(list(gc.EXACT_CASES) + list(gc.CHAINS), got):
+        assert g[0] == c.claims, (c.name, g)
+    rings = {g[2][0] for c, g in zip(gc.EXACT_CASES, got) if c in gc.TINY}
+    assert rings == {2, 3, 4}, rings
+
+
+SPOT_SHAPES = [   # (M, N, K, epi, ldx, ldw, ln_part, no_split, ncu): the shapes of test_dispatch_mirror_on_the_documented_shapes
+    (19152, 1024, 1024, gc.LS_RES, 1024, 1024, 0, 0, 256), (19152, 1024, 1024, gc.LS_RES, 1024, 1024, 0, 1, 256),
+    (6 * 1376, 1024, 1024, gc.BIAS, 1024, 1024, 0, 0, 256), (1370 + 6, 1024, 1024, gc.BIAS, 1024, 1024, 0, 0, 256),
+    (70000, 1024, 1024, gc.BIAS, 1024, 1024, 0, 0, 256), (70000, 1024, 1024, gc.BIAS, 1024, 1024, 0, 1, 256),
+    (70000, 1024, 4096, gc.LS_RES, 4096, 4096, 0, 1, 256), (70000, 1024, 4096, gc.LS_RES, 4096 + 8, 4096, 0, 1, 256),
+    (65536, 1024, 1024, gc.BIAS, 1024, 1024, 0, 0, 256), (2600, 1024, 4096, gc.LS_RES, 4096, 4096, 0, 0, 256),
+    (52 * 1376, 1024, 1024, gc.VT, 1024, 1024, 0, 0, 256), (49152, 256, 256, gc.LN_BIAS, 256, 256, 1, 0, 256),
+    (49151 - 255, 256, 256, gc.LN_BIAS, 256, 256, 1, 0, 256), (48897, 256, 64, gc.BIAS, 64, 64, 0, 1, 304),
+]
+
+
+def test_plan_on_the_documented_shapes(plan_check):
+    got = _assert_plans_equal_mirror(plan_check, SPOT_SHAPES)
+    assert [g[0] for g in got] == ["split_big+tiny64", "small128", "split_mid+tiny64", "tiny64", "split_big+small128", "big_hip_stream", "big_asm",
+                                   "big_hip_stream", "big_hip", "tiny64", "big_hip_stream", "finalize_then_big_hip", "split_mid+tiny64", "small128"]
+    assert got[0][1] == 16384 and got[0][3] == (256, 704)          # one whole round of 256 big tiles, 2768 rows on 44 x 16 one-wave tiles
+    assert got[3][2] == (4, 0) and got[3][3] == (22 * 16, 0)       # one 518^2 crop: 352 tiles of 64x64 on the deepest ring
+
+
+def sweep_shapes(n=120000, seed=20261):
+    """seeded: M log-uniform in [1, 400 000] or k 128 or k 256 +- 1; N 16 .. 8192 with ragged values; K in {64, 256, 1024, 2048, 4096}; all nine
+    epilogues (their own constraints kept: N % 64 for the LN / statistics / V^T forms, M % 16 for V^T, M >= 16 for LN); ln_part on half the
+    LN launches; row split on and off; ldx in {K, K + 8}; 32 .. 304 CUs"""
+    g = np.random.default_rng(seed)
+    kind = g.integers(0, 3, n)
+    m_log = np.exp(g.uniform(0.0, np.log(400000.0), n)).astype(np.int64)
+    m_128 = g.integers(1, 400000 // 128 + 1, n) * 128
+    m_256 = g.integers(1, 400000 // 256, n) * 256 + g.choice([-1, 1], n)
+    M = np.clip(np.where(kind == 0, m_log, np.where(kind == 1, m_128, m_256)), 1, 400000)
+    n_any = np.array([16, 48, 80, 144, 256, 272, 384, 400, 768, 1024, 1040, 1536, 1936, 2048, 3072, 4096, 4112, 8176, 8192])
+    n_64 = np.array([64, 192, 256, 320, 384, 768, 1024, 1088, 1536, 1984, 2048, 3072, 4096, 4160, 8128, 8192])
+    epi = g.integers(0, 9, n)
+    plain = np.isin(epi, (gc.BIAS, gc.GELU, gc.LS_RES, gc.PATCH))
+    N = np.where(plain, g.choice(n_any, n), g.choice(n_64, n))
+    trans = np.isin(epi, (gc.VT, gc.LN_VT))
+    M = np.where(trans, cdiv16(M), M)
+    M = np.where(np.isin(epi, LN_EPIS), np.maximum(M, 16), M)
+    K = g.choice([64, 256, 1024, 2048, 4096], n)
+    ldx = K + 8 * g.integers(0, 2, n)
+    ln_part = np.isin(epi, LN_EPIS) & (g.integers(0, 2, n) == 1)
+    no_split = g.integers(0, 2, n)
+    ncu = g.choice([32, 64, 120, 256, 304], n)
+    return [tuple(int(v) for v in row) for row in zip(M, N, K, epi, ldx, K, ln_part, no_split, ncu)]
+
+
+def cdiv16(m):
+    return (m + 15) // 16 * 16
+
+
+# Every form of label the sweep must produce, so that it cannot silently cover one side of a threshold only: the five tiers and both splits
+# with each remainder tier that occurs.  The remainder of a split_big is less than a round + one row of tiles, which can still be a filled
+# round (big_hip, big_asm) but never 128 MiB of output; a split_mid whose remainder fills the CUs with 128x128 tiles saves no round, so its
+# remainder is always tiny64.  FINALIZED: what follows finalize_then_ — V^T launches on any tier, row-major ones from 192 big tiles on;
+# never big_asm (the product has no hand-scheduled LN kernel) and with it no split_big+big_asm.
+SWEEP_LABELS = {"tiny64", "small128", "big_hip", "big_hip_stream", "big_asm", "split_big+tiny64", "split_big+small128", "split_big+big_hip",
+                "split_big+big_asm", "split_mid+tiny64"}
+FINALIZED = {"tiny64", "small128", "big_hip", "big_hip_stream", "split_big+tiny64", "split_big+small128", "split_big+big_hip", "split_mid+tiny64"}
+
+
+def test_plan_equals_mirror_on_a_sweep(plan_check):
+    shapes = sweep_shapes()
+    assert len(shapes) >= 100000
+    got = _assert_plans_equal_mirror(plan_check, shapes)
+    labels = {g[0] for g in got}
+    plain = {lb for lb in labels if not lb.startswith("finalize_then_")}
+    assert plain == SWEEP_LABELS, sorted(plain ^ SWEEP_LABELS)
+    fin = {lb[len("finalize_then_"):] for lb in labels - plain}
+    assert fin == FINALIZED, sorted(fin ^ FINALIZED)
+    for s, g in zip(shapes, got):                                                 # what a split and a finalisation are for
+        if g[0].startswith("finalize_then_"):
+            assert s[6] and s[3] in LN_EPIS
+        if g[1]:
+            assert not s[7] and s[3] not in (gc.VT, gc.LN_VT, gc.PATCH) and 0 < g[1] < s[0]
+
+
 def test_dispatch_mirror_on_the_documented_shapes():
-    """shapes whose path the sources state in words (gemm_bf16.hip launch_epi, tests/test_gpu_kernels.py)"""
+    """shapes whose path the sources state in words (csrc/gemm_plan.h, tests/test_gpu_kernels.py)"""
     assert gc.branch(19152, 1024, 1024, gc.LS_RES) == "split_big+tiny64"          # the video path's ~20-crop batches
     assert gc.branch(19152, 1024, 1024, gc.LS_RES, row_split=False) == "small128"
     assert gc.branch(6 * 1376, 1024, 1024, gc.BIAS) == "split_mid+tiny64"         # 520 tiles = one 128x128 round + 8

@@ -1,8 +1,11 @@
 """Every tile tier, epilogue and row split of the ViT GEMM family (csrc/gemm_bf16.hip, gemm_epilogue.h, gemm_asm.hip) against exact arithmetic,
 bit for bit, through the C entries with leading dimensions and guards under the test's control; and the LayerNorm chain (LS_RES_STATS
 producer -> LN-folded consumer) on both routes the partial row statistics can take.  Cases, references and the dispatch mirror live in
-tests/_gemm_cases.py; tests/test_gemm_cases_cpu.py shows without a GPU that every case reaches the branch named here on 256 CUs ; on a
-device with another CU count a case whose shape would reach another branch fails with that message instead of passing on the wrong tier.
+tests/_gemm_cases.py; tests/test_gemm_cases_cpu.py shows without a GPU that the library's statement of the dispatch (csrc/gemm_plan.h) sends
+every case to the branch named here on 256 CUs, on the ring depths named here, and equals the mirror on 10^5 shapes.  Here every test first
+asks the library which plan it executes for its launch on this device (fp_op_gemm_plan, _assert_claim): on a device with another CU count a
+case whose shape would reach another branch fails with that message instead of passing on the wrong tier, and the split tests take the
+split row from the library.
 
 Outputs are allocated with ldc > N and 64 extra rows, filled with 0xFF bytes (a NaN pattern no case produces): the [M, N] block must equal the
 reference, every other byte must still hold the poison.  Input padding columns (ldx > K, ldw > K, ldr > N) hold NaN: a read outside an operand
@@ -53,10 +56,22 @@ def _api():
     return _lib.load(), ops
 
 
-def _assert_claim(name, got, claims, ncu):
-    """the shapes are chosen for 256 CUs; on another count a case that would reach another branch fails here instead of passing on the wrong
-    tier (derive its shape anew from _gemm_cases.branch(..., n_cu=ncu))"""
-    assert got == claims, f"{name}: on {ncu} CUs this shape reaches {got}, not {claims}; derive the shape from _gemm_cases.branch for this device"
+def _assert_claim(case, claims, ncu):
+    """The library itself says which plan it executes for this launch on this device (fp_op_gemm_plan: the function fp_gemm_bf16 launches
+    from): it must be the branch the case is there for, and the mirror must say the same.  The shapes are chosen for 256 CUs; on another
+    count a case that would reach another branch fails here instead of passing on the wrong tier (derive its shape anew from
+    _gemm_cases.branch(..., n_cu=ncu)).  Returns the plan."""
+    from freepose_amd import ops
+    if isinstance(case, gc.Chain):                                                # the consumer launch with the partial sums handed over
+        plan = ops.gemm_plan(case.M, case.N2, case.D, gc.LN_BIAS if case.mode == 0 else gc.LN_GELU, ln_part=True)
+        mirror = case.branch(ncu, ln_part=True)
+    else:
+        plan = ops.gemm_plan(case.M, case.N, case.K, case.epi, case.ld("x"), case.ld("w"))
+        mirror = case.branch(ncu)
+    got = plan["label"]
+    assert got == claims, f"{case.name}: on {ncu} CUs this shape reaches {got}, not {claims}; derive the shape from _gemm_cases.branch for this device"
+    assert mirror == got, f"{case.name}: the library runs {plan['text']}, tests/_gemm_cases.py says {mirror}"
+    return plan
 
 
 def _poison(rows, ld):
@@ -117,7 +132,7 @@ def _assert_guards(case, cbuf, M, N):
 def _run_plain(case, ncu, gelu_tab):
     """BIAS / GELU / LS_RES through fp_op_gemm, LS_RES_STATS through fp_op_gemm_stats; returns the decoded statistics for the latter"""
     lib, ops = _api()
-    _assert_claim(case.name, case.branch(ncu), case.claims, ncu)
+    plan = _assert_claim(case, case.claims, ncu)
     M, N, K = case.M, case.N, case.K
     x, w, bias = _operands(case)
     gamma = resid = None
@@ -136,7 +151,8 @@ def _run_plain(case, ncu, gelu_tab):
                                  ops.ptr(gamma), ops.ptr(resid), case.ld("r"), M, N, K, {gc.BIAS: 0, gc.GELU: 1, gc.LS_RES: 2}[case.epi],
                                  ops.current_stream()), "fp_op_gemm")
     torch.cuda.synchronize()
-    rows = gc.check_rows(case, ncu)
+    assert gc.split_point(M, N, ncu) == plan["row0"], f"{case.name}: the library splits at row {plan['row0']}, the mirror at {gc.split_point(M, N, ncu)}"
+    rows = gc.check_rows(case, ncu, split_row=plan["row0"])
     blocks = _assert_rows(case, cbuf, rows, gelu_tab)
     _assert_guards(case, cbuf, M, N)
     if case.epi == gc.LS_RES_STATS:
@@ -193,7 +209,7 @@ def test_row_splits(case, ncu, gelu_tab):
 @pytest.mark.parametrize("case", gc.VT_CASES, **_ids)
 def test_vt(case, ncu, gelu_tab):
     lib, ops = _api()
-    _assert_claim(case.name, case.branch(ncu), case.claims, ncu)
+    _assert_claim(case, case.claims, ncu)
     M, N, K, npad, H = case.M, case.N, case.K, case.npad, case.heads
     B = M // npad
     x, w, bias = _operands(case)
@@ -218,7 +234,7 @@ def test_vt(case, ncu, gelu_tab):
 @pytest.mark.parametrize("case", gc.PATCH_CASES, **_ids)
 def test_patch(case, ncu, gelu_tab):
     lib, ops = _api()
-    _assert_claim(case.name, case.branch(ncu), case.claims, ncu)
+    _assert_claim(case, case.claims, ncu)
     M, N, K, P, npad, off = case.M, case.N, case.K, case.P, case.npad, case.tok_off
     B = M // P
     x, w, bias = _operands(case)
@@ -276,7 +292,7 @@ def test_ln_chain(ch, ncu, gelu_tab):
     output (for example got 2.03125 against 2.0474: half an ulp of 2^-6 is the dominant term of the bound), so the ratios approach 1
     from the output rounding alone, not from the statistics."""
     import dataclasses
-    _assert_claim(ch.name, ch.branch(ncu, ln_part=True), ch.claims, ncu)
+    _assert_claim(ch, ch.claims, ncu)
     prod = dataclasses.replace(ch.producer, subset=ch.M > 10000)
     w2, b2, g_ln, b_ln = gc.chain_operands(ch)
     x1, w1, b1 = _operands(prod)
