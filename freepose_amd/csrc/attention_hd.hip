@@ -185,11 +185,7 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(AttnHdArgs p) {
             float e[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) e[j] = __builtin_amdgcn_exp2f(s[2 * ks + (j >> 2)][j & 3] - mnew);   // masked: exp2(-1e30) = 0
-            uint4 w;
-            w.x = pack_bf2(e[0], e[1]);
-            w.y = pack_bf2(e[2], e[3]);
-            w.z = pack_bf2(e[4], e[5]);
-            w.w = pack_bf2(e[6], e[7]);
+            const uint4 w = pack_bf8(e);
             // the sum runs over the bf16 values the second product multiplies by
             lsum += ((lo_bf(w.x) + hi_bf(w.x)) + (lo_bf(w.y) + hi_bf(w.y))) + ((lo_bf(w.z) + hi_bf(w.z)) + (lo_bf(w.w) + hi_bf(w.w)));
             pf[ks] = __builtin_bit_cast(bf16x8_t, w);

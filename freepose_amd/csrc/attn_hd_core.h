@@ -6,11 +6,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define FP_HD __host__ __device__ __forceinline__
-#else
-#define FP_HD static inline
-#endif
+#include "attn_core.h"   // FP_HD, and the fragment geometry this kernel shares with attention.hip
 
 #define FP_AHD_KEY_TILE 64
 
@@ -24,10 +20,9 @@ FP_HD int fp_ahd_num_tiles(int n_tok) { return (n_tok + FP_AHD_KEY_TILE - 1) / F
 FP_HD bool fp_ahd_row_real(int row, int n_tok) { return row < n_tok; }
 // a 16-byte chunk of 8 features starting at d0 that belongs to the head (hd % 8 == 0: wholly inside or wholly outside)
 FP_HD bool fp_ahd_chunk_real(int d0, int hd) { return d0 < hd; }
-// K fragment fk (0..3), MFMA A-row i (0..15)  ->  key row inside the 64-key tile
-FP_HD int fp_ahd_tile_key(int fk, int i) { return 32 * (fk >> 1) + 8 * (i >> 2) + 4 * (fk & 1) + (i & 3); }
-// accumulator register r of fragment fk on a lane of 16-lane row lg  ->  key inside the tile (C row 4 lg + r of that fragment)
-FP_HD int fp_ahd_acc_key(int fk, int lg, int r) { return fp_ahd_tile_key(fk, 4 * lg + r); }
+// K fragment fk, MFMA A-row i -> key row inside the tile; accumulator register r of fragment fk on 16-lane row lg -> key inside the tile
+FP_HD int fp_ahd_tile_key(int fk, int i) { return fp_attn_tile_key(fk, i); }
+FP_HD int fp_ahd_acc_key(int fk, int lg, int r) { return fp_attn_acc_key(fk, lg, r); }
 
 
 // ---- LDS images of one key tile and the staging that fills them.  nch = 16-byte chunks per padded row (4 per 32-wide k step).

@@ -621,7 +621,6 @@ extern "C" int fp_op_gelu(const void* x, void* y, size_t n, void* stream) {
 }
 extern "C" int fp_op_attention(const void* QK, int ldqk, const void* Vt, void* O, int ldo, int B, int H, int n_tok,
                                int npad, int q_prescaled, void* stream) {
-    FP_REQUIRE(QK && Vt && O, "op_attention: null argument");
     return fp_attention_fwd((const bf16_t*)QK, ldqk, (const bf16_t*)Vt, (bf16_t*)O, ldo, B, H, n_tok, npad, q_prescaled != 0,
                             (hipStream_t)stream);
 }

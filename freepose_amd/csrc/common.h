@@ -48,6 +48,10 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
     v[1] = static_cast<__bf16>(hi);
     return __builtin_bit_cast(uint32_t, v);  // one v_cvt_pk_bf16_f32
 }
+// eight consecutive values as one 16-byte word (an MFMA operand's eight contraction slots, or a row store)
+__device__ __forceinline__ uint4 pack_bf8(const float (&e)[8]) {
+    return make_uint4(pack_bf2(e[0], e[1]), pack_bf2(e[2], e[3]), pack_bf2(e[4], e[5]), pack_bf2(e[6], e[7]));
+}
 __device__ __forceinline__ float lo_bf(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float hi_bf(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 

@@ -61,6 +61,40 @@ def test_xcd_remap_is_a_bijection(nwg):
     assert sorted(ac.xcd_remap(nwg)) == list(range(nwg))
 
 
+def test_dispatch_mirror_against_the_kernel_header(tmp_path):
+    """tools/attn_host_check.cpp — csrc/attn_core.h, the functions attention.hip and its launcher call — built with
+    -fsanitize=address,undefined as a stand-alone program: its own checks pass (block remap, tile order, LDS maps replayed on a labelled
+    host image, clamped staging, mask, wait ladder), and the dispatch records it prints are what dino_dispatch / xcd_remap say"""
+    import shutil
+    import subprocess
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    gxx = shutil.which("g++")
+    assert gxx, "g++ not found"
+    exe = tmp_path / "attn_host_check"
+    r = subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", str(root / "freepose_amd" / "csrc"),
+                        str(root / "tools" / "attn_host_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    shapes = list(ac.DINO_SHAPES) + [(B, H, n) for B, H in ((1, 1), (2, 3)) for n in range(1, 2049)]
+    args = [f"{B},{H},{n}" for B, H, n in ac.DINO_SHAPES] + ["1,1,1-2048", "2,3,1-2048"]
+    r = subprocess.run([str(exe), *args], capture_output=True, text=True)
+    assert r.returncode == 0 and "attn_host_check: ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("dispatch ")]
+    assert len(lines) == len(shapes)
+    for (B, H, n), ln in zip(shapes, lines):
+        head, order, remap = (part.split() for part in ln.split("|"))
+        d = ac.dino_dispatch(B, H, n)
+        assert [int(x) for x in head[1:]] == [B, H, n, d.npad, d.ntile, d.short_tail, d.clamped_last, d.idle_waves, d.half_waves, d.nwg], ln[:120]
+        assert tuple(int(x) for x in order) == d.tile_order, (B, H, n)
+        assert [int(x) for x in remap] == ac.xcd_remap(d.nwg), (B, H, n)
+    # the kernel and its launcher take these from the header, not from expressions of their own
+    src = (root / "freepose_amd" / "csrc" / "attention.hip").read_text()
+    for fn in ("fp_attn_product_flavour", "fp_attn_grid", "fp_attn_block_remap", "fp_attn_block_of", "fp_attn_wave_q0", "fp_attn_wave_idle", "fp_attn_num_tiles",
+               "fp_attn_tile_of", "fp_attn_in_flight", "fp_attn_stage_clamped", "fp_attn_clamp_key", "fp_attn_clamp_group", "fp_attn_dma_row", "fp_attn_dma_base",
+               "fp_attn_dma_kchunk", "fp_attn_dma_vchunk", "fp_attn_frag_chunk", "fp_attn_kfrag_step", "fp_attn_vfrag_step", "fp_attn_acc_key"):
+        assert fn + "(" in src, fn
+
+
 def test_hd_and_causal_shape_lists_reach_every_branch():
     hd = {(d, n): ac.hd_dispatch(d, n) for d in ac.HD_DIMS for n in ac.HD_NTOK}
     assert {x.nkk for x in hd.values()} == {1, 2, 3, 4}

@@ -42,6 +42,38 @@ def test_impossible_requests_fail_loudly():
         ops.attention(torch.zeros((0, 128), dtype=bf).cuda(), torch.zeros((0, 1, 64, 16), dtype=bf).cuda(), 16)
 
 
+def test_attention_entry_refuses_null_pointers_and_bad_leading_dimensions():
+    """fp_op_attention returns an error that names the argument, before any launch (the output keeps its fill), for a null pointer, a
+    leading dimension that is no multiple of 8 (the kernel reads and writes 16-byte vectors) and one narrower than the rows it addresses"""
+    from freepose_amd import _lib
+    lib = _lib.load()
+    B, H, n_tok, npad = 1, 1, 16, 16
+    qk = torch.zeros((B * npad, 2 * H * 64 + 8), dtype=torch.bfloat16, device="cuda")
+    vt = torch.zeros((B, H, 64, npad), dtype=torch.bfloat16, device="cuda")
+    out = torch.full((B * npad, H * 64 + 8), 7.0, dtype=torch.bfloat16, device="cuda")
+
+    def refused(name, qk_=qk, ldqk=2 * H * 64, vt_=vt, out_=out, ldo=H * 64):
+        for pre in (0, 1):
+            with pytest.raises(RuntimeError, match=rf"attention: .*\b{name}\b"):
+                _lib.check(lib.fp_op_attention(_lib.ptr(qk_), ldqk, _lib.ptr(vt_), _lib.ptr(out_), ldo, B, H, n_tok, npad, pre, _lib.current_stream()),
+                           "fp_op_attention")
+
+    refused("QK", qk_=None)
+    refused("Vt", vt_=None)
+    refused("O", out_=None)
+    refused("ldqk", ldqk=2 * H * 64 + 4)
+    refused("ldqk", ldqk=2 * H * 64 - 8)
+    refused("ldo", ldo=H * 64 + 4)
+    refused("ldo", ldo=H * 64 - 8)
+    torch.cuda.synchronize()
+    assert (out == 7.0).all()
+    # the same buffers with the dimensions they have are accepted
+    _lib.check(lib.fp_op_attention(_lib.ptr(qk), 2 * H * 64 + 8, _lib.ptr(vt), _lib.ptr(out), H * 64 + 8, B, H, n_tok, npad, 0, _lib.current_stream()),
+               "fp_op_attention")
+    torch.cuda.synchronize()
+    assert (out[:, :64] == 0).all() and (out[:, 64:] == 7.0).all()
+
+
 def test_fully_masked_and_degenerate_boxes():
     """a proposal whose mask is empty gives a NaN descriptor (0/0 like the reference's masked mean); a zero-area box gives an
     all-zero crop instead of reading out of bounds"""
