@@ -124,6 +124,7 @@ SIGNATURES = {
                                  c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "fp_op_workspace_read": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
     "fp_op_gemm_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
+    "fp_op_raster_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_char_p, c_size_t]),
     "fp_op_gelu": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "fp_op_attention": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fp_op_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

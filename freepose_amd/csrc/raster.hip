@@ -49,6 +49,7 @@
 // rasterised by their thread, large ones by a whole wave via a queue), resolve kernel (Hn x pixels).
 #include "../../include/freepose_hip.h"
 #include "internal.h"
+#include "raster_plan.h"   // the launch arithmetic and every threshold the kernels branch on, stated once (checked on a CPU)
 
 #include <algorithm>
 
@@ -81,8 +82,10 @@ namespace {
 struct SVert { int xi, yi; float iz, zc; };
 struct RasterView { float R[9]; float t[3]; };
 
-constexpr float ZNEAR = 0.05f;
-constexpr int BIG_AREA = 256;  // bbox pixels above which a triangle goes to the wave-per-triangle queue
+using fp_raster::ZNEAR;
+using fp_raster::BIG_AREA;     // bbox pixels above which a triangle goes to the wave-per-triangle queue
+using fp_raster::CLAMP_PX;
+using fp_raster::SMALL_SPAN;
 
 __global__ void raster_vertex_kernel(const float* __restrict__ verts, int V, const float* __restrict__ poses, int Hn,
                                      float scale, float fx, float fy, float cx, float cy, SVert* __restrict__ sv) {
@@ -100,7 +103,7 @@ __global__ void raster_vertex_kernel(const float* __restrict__ verts, int V, con
         const float iz = 1.0f / Zc;
         const float u = fmaf(fx, Xc * iz, cx), v = fmaf(fy, Yc * iz, cy);
         // clamp far-off-screen coordinates so the fixed-point products stay inside int64
-        const float uc = fminf(fmaxf(u, -30000.f), 30000.f), vc = fminf(fmaxf(v, -30000.f), 30000.f);
+        const float uc = fminf(fmaxf(u, -CLAMP_PX), CLAMP_PX), vc = fminf(fmaxf(v, -CLAMP_PX), CLAMP_PX);
         o.xi = (int)rintf(uc * 256.0f);
         o.yi = (int)rintf(vc * 256.0f);
         o.iz = iz;
@@ -205,7 +208,7 @@ __device__ __forceinline__ TriSetup tri_setup_v(SVert a, SVert b, SVert c, int i
     t.bx1 = min(W - 1, (mxx - 128) >> 8);
     t.by1 = min(Hh - 1, (mxy - 128) >> 8);
     if (t.bx1 < t.bx0 || t.by1 < t.by0) t.ok = false;
-    t.small = (mxx - mnx) < 32768 && (mxy - mny) < 32768;
+    t.small = (mxx - mnx) < SMALL_SPAN && (mxy - mny) < SMALL_SPAN;
     return t;
 }
 __device__ __forceinline__ TriSetup tri_setup(const SVert* __restrict__ sv, const int32_t* __restrict__ faces, int f,
@@ -571,24 +574,20 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const SVert* __rest
 //                 optional: the pose hot path needs only the extents (pose_estimator.py:104-112) and the crops.
 // Same tri_setup / tri_cover / tri_depth, same candidate pixel set (bbox ∩ tile over all tiles = bbox), same 64-bit key and
 // an order-independent minimum: the output is bit-identical to the global-buffer path and to the oracle.
-constexpr int BIN_CHUNK = 64;
-constexpr int BIG_TILE_AREA = 32;       // candidate pixels in the tile above which a triangle is handed to the whole wave
-constexpr int HITS_ROUND = 2048;         // chunk masks examined per round of the tile kernel (8 per thread; 16-bit ids relative to the round's base)
+using fp_raster::BIN_CHUNK;
+using fp_raster::BIG_TILE_AREA;          // candidate pixels in the tile above which a triangle is handed to the whole wave
+using fp_raster::HITS_ROUND;             // chunk masks examined per round of the tile kernel (8 per thread; 16-bit ids relative to the round's base)
+static_assert(fp_raster::BIN_WAVES * 64 == 256 && fp_raster::TILE_THREADS == 256 && HITS_ROUND % fp_raster::TILE_THREADS == 0 &&
+                  HITS_ROUND <= 65536 && BIG_TILE_AREA <= 32 && BIN_CHUNK == 64 && 2 * fp_raster::TILE_MAX <= fp_raster::TILE_THREADS &&
+                  fp_raster::TILES_SIDE == 8 && fp_raster::tile_lds(fp_raster::TILE_MAX) <= (size_t)fp_raster::LDS_BUDGET,
+              "raster_plan.h describes other kernels");
 constexpr uint16_t TBOX_NONE = 0x000f;   // tx0 = 15 > tx1 = 0: overlaps nothing
 constexpr int PART_N = 10;               // doubles per (view, tile) extents record
 
 // Workgroup -> (item, view) with all items of a view on ONE XCD: workgroup L of a launch runs on XCD L % 8 (observed; a speed hint
 // only, MI355X_MICROARCH.md "Workgroup dispatch"), so within a group of 8 views the linear id walks the views fastest.
 __device__ __forceinline__ void view_major_ids(int nx, int Hn, int& item, int& h) {
-    const int L = blockIdx.y * nx + blockIdx.x;
-    const int full = Hn & ~7, per_group = 8 * nx;
-    if (L < (full >> 3) * per_group) {
-        const int g = L / per_group, r = L - g * per_group;
-        h = g * 8 + (r & 7); item = r >> 3;
-    } else {
-        const int r = L - (full >> 3) * per_group;
-        h = full + r / nx; item = r - (r / nx) * nx;
-    }
+    fp_raster::view_major(blockIdx.y * nx + blockIdx.x, nx, Hn, item, h);   // (stated in raster_plan.h: the host check walks it over whole grids)
 }
 
 __device__ __forceinline__ unsigned long long wave_or64(unsigned long long m) {
@@ -1268,25 +1267,23 @@ static int rasterize_impl(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses
     FP_LAUNCH_CHECK();
     const bool want_ext = d_ext || d_boxes;
 
-    // tile edge: 64 px up to 512-px images, else the smallest multiple of 8 that covers the image with 8 x 8 tiles
-    const int side = W > Hh ? W : Hh;
-    const int T = side <= 512 ? 64 : (cdiv(side, 8) + 7) / 8 * 8;
+    // The launch arithmetic is fp_raster::make_plan (raster_plan.h): tile edge 64 px up to 512-px images, else the smallest multiple of
+    // 8 that covers the image with 8 x 8 tiles.
     // fp_ctx_set_option(ctx, "raster_tiled", v): -1 / unset = tiled for images of up to 8 x 8 tiles of <= 88 px and meshes of up to
     // 131 072 triangles, 0 = global visibility buffer, 1 = tiled.  Measured, 576 views @420^2 with boxes + extents (ms; tiled | global,
     // profiles/r06_raster_perf.log): 1 280 triangles 1.64 | 2.57, 20 480: 1.65 | 2.70, 81 920: 2.28 | 2.40, 327 680: 5.04 | 2.81 —
     // both are bound by vector instructions, the tiled path per triangle (set-up in the bin AND the tile kernel, ~1.6 tiles per chunk of
     // 64), the global path per fragment (L2 atomics).  Rounds 1-5 stopped at 32 768 triangles.
-    const int mode = ctx->opt_raster_tiled;
-    const bool tiled = T <= 88 && (mode == 1 || (mode != 0 && F <= 131072));
-    if (tiled) {
-        const int ntx = cdiv(W, T), nty = cdiv(Hh, T), ntile = ntx * nty, nchunk = cdiv(F, BIN_CHUNK);
+    const fp_raster::Plan plan = fp_raster::make_plan(W, Hh, F, Hn, ctx->opt_raster_tiled);
+    if (plan.tiled) {
+        const int T = plan.T, ntx = plan.ntx, ntile = plan.ntile, nchunk = plan.nchunk;
         uint16_t* tbox;
         unsigned long long* cmask;
         double* part = nullptr;
         if ((rc = ctx->get("raster.tbox", (size_t)Hn * nchunk * BIN_CHUNK * 2, (void**)&tbox))) return rc;
         if ((rc = ctx->get("raster.cmask", (size_t)Hn * nchunk * 8, (void**)&cmask))) return rc;
         if (want_ext && (rc = ctx->get("raster.part", (size_t)Hn * ntile * PART_N * 8, (void**)&part))) return rc;
-        hipLaunchKernelGGL(raster_bin_kernel, dim3(cdiv(nchunk, 4), Hn), dim3(256), 0, s, sv, mesh->faces, mesh->perm, mesh->fsort, V, F, W, Hh, T, Hn,
+        hipLaunchKernelGGL(raster_bin_kernel, dim3(plan.bin_grid, Hn), dim3(256), 0, s, sv, mesh->faces, mesh->perm, mesh->fsort, V, F, W, Hh, T, Hn,
                            nchunk, tbox, cmask, mesh->cull);
         FP_LAUNCH_CHECK();
         unsigned long long* dbg_buf = nullptr;
@@ -1299,9 +1296,8 @@ static int rasterize_impl(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses
 #else
         const int raster_dbg = 0;
 #endif
-        const size_t lds = (size_t)T * T * 8 + 2048 + HITS_ROUND * 2 + (size_t)2 * T * 8;   // keys + DEC/THR tables + hit list + column / row factors
-        FP_DYN_LDS_ONCE(raster_tile_kernel, 88 * 88 * 8 + 2048 + HITS_ROUND * 2 + 2 * 88 * 8);
-        hipLaunchKernelGGL(raster_tile_kernel, dim3(ntile, Hn), dim3(256), lds, s, sv, mesh->faces, mesh->perm, mesh->fsort, shade_args(mesh), mesh->tables,
+        FP_DYN_LDS_ONCE(raster_tile_kernel, (int)fp_raster::tile_lds(fp_raster::TILE_MAX));
+        hipLaunchKernelGGL(raster_tile_kernel, dim3(ntile, Hn), dim3(256), plan.lds, s, sv, mesh->faces, mesh->perm, mesh->fsort, shade_args(mesh), mesh->tables,
                            V, F, W, Hh, T, ntx, Hn, tbox, cmask, nchunk, d_rgb, d_depth, part, (double)fx, (double)fy, (double)cx, (double)cy, raster_dbg & ~(1 << 30), dbg_buf);
         FP_LAUNCH_CHECK();
         if (want_ext) {
@@ -1356,6 +1352,17 @@ extern "C" int fp_rasterize_extents(fp_ctx* ctx, const fp_mesh* mesh, const floa
     FP_REQUIRE(W > 0 && Hh > 0 && W <= 8192 && Hh <= 8192, "rasterize_extents: bad image size");
     if (Hn == 0) return FP_OK;
     return rasterize_impl(ctx, mesh, d_poses, Hn, scale, fx, fy, cx, cy, W, Hh, d_rgb, d_depth, d_ext, d_boxes, (hipStream_t)stream);
+}
+
+// The plan rasterize_impl would execute for F triangles and Hn views on a W x H frame under this context's "raster_tiled", in words
+// (raster_plan.h plan_text), with the thresholds the kernels were compiled with: nothing is launched.  What the tests of the
+// rasteriser's branches hold their case table to.
+extern "C" int fp_op_raster_plan(fp_ctx* ctx, int W, int H, int F, int Hn, char* out, size_t out_bytes) {
+    FP_REQUIRE(ctx && out && out_bytes > 0, "op_raster_plan: null argument");
+    FP_REQUIRE(W > 0 && H > 0 && W <= 8192 && H <= 8192 && F > 0 && Hn >= 0, "op_raster_plan: W=%d H=%d F=%d Hn=%d", W, H, F, Hn);
+    const int n = fp_raster::plan_text(fp_raster::make_plan(W, H, F, Hn, ctx->opt_raster_tiled), out, out_bytes);
+    FP_REQUIRE(n >= 0 && (size_t)n < out_bytes, "op_raster_plan: the text needs %d bytes", n + 1);
+    return FP_OK;
 }
 
 extern "C" int fp_mesh_set_ambient(fp_mesh* mesh, float ambient) {

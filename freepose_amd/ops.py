@@ -390,13 +390,24 @@ class Mesh:
             pass
 
 
-def rasterize(mesh: Mesh, poses: torch.Tensor, scale: float, fx: float, fy: float, cx: float, cy: float, W: int, H: int):
-    """poses [Hn,4,4] object->camera (OpenCV).  Returns (rgb u8 [Hn,H,W,3], depth f32 [Hn,H,W]) on device."""
+def _raster_out(out, n, shapes, dtypes, device):
+    """the output tensors of a rasteriser call: fresh ones, or the caller's (`out`: contiguous device tensors of these shapes and types;
+    None entries are passed on as "not wanted")"""
+    if out is None:
+        return [torch.empty(s, dtype=d, device=device) for s, d in zip(shapes, dtypes)]
+    assert len(out) == n
+    for t, s, d in zip(out, shapes, dtypes):
+        assert t is None or (t.is_cuda and t.is_contiguous() and tuple(t.shape) == tuple(s) and t.dtype == d), (s, d)
+    return list(out)
+
+
+def rasterize(mesh: Mesh, poses: torch.Tensor, scale: float, fx: float, fy: float, cx: float, cy: float, W: int, H: int, out=None):
+    """poses [Hn,4,4] object->camera (OpenCV).  Returns (rgb u8 [Hn,H,W,3], depth f32 [Hn,H,W]) on device; `out` = (rgb, depth) to
+    write into (every element is written)."""
     lib = _lib.load()
     p = _dev(torch.as_tensor(poses), torch.float32)
     Hn = p.shape[0]
-    rgb = torch.empty((Hn, H, W, 3), dtype=torch.uint8, device=p.device)
-    depth = torch.empty((Hn, H, W), dtype=torch.float32, device=p.device)
+    rgb, depth = _raster_out(out, 2, [(Hn, H, W, 3), (Hn, H, W)], [torch.uint8, torch.float32], p.device)
     if Hn:
         check(lib.fp_rasterize(context(), mesh.handle, ptr(p), Hn, float(scale), float(fx), float(fy), float(cx), float(cy),
                                int(W), int(H), ptr(rgb), ptr(depth), current_stream()), "fp_rasterize")
@@ -404,17 +415,20 @@ def rasterize(mesh: Mesh, poses: torch.Tensor, scale: float, fx: float, fy: floa
 
 
 def rasterize_extents(mesh: Mesh, poses: torch.Tensor, scale: float, fx: float, fy: float, cx: float, cy: float, W: int, H: int,
-                      want_depth: bool = False):
+                      want_depth: bool = False, out=None):
     """rasterize() with the depth image's consumers fused into the tile epilogue: returns (rgb u8 [Hn,H,W,3], depth f32 [Hn,H,W] or
     None, ext f64 [Hn,8] == depth_extents(depth), boxes i32 [Hn,4] == ext[:, :4]).  Without `want_depth` the depth image is never
-    written (the pose hot path needs only the extents)."""
+    written (the pose hot path needs only the extents).  `out` = (rgb, depth | None, ext, boxes) to write into."""
     lib = _lib.load()
     p = _dev(torch.as_tensor(poses), torch.float32)
     Hn = p.shape[0]
-    rgb = torch.empty((Hn, H, W, 3), dtype=torch.uint8, device=p.device)
-    depth = torch.empty((Hn, H, W), dtype=torch.float32, device=p.device) if want_depth else None
-    ext = torch.empty((Hn, 8), dtype=torch.float64, device=p.device)
-    boxes = torch.empty((Hn, 4), dtype=torch.int32, device=p.device)
+    if out is None:
+        out = (torch.empty((Hn, H, W, 3), dtype=torch.uint8, device=p.device),
+               torch.empty((Hn, H, W), dtype=torch.float32, device=p.device) if want_depth else None,
+               torch.empty((Hn, 8), dtype=torch.float64, device=p.device), torch.empty((Hn, 4), dtype=torch.int32, device=p.device))
+    assert (out[1] is not None) == bool(want_depth)
+    rgb, depth, ext, boxes = _raster_out(out, 4, [(Hn, H, W, 3), (Hn, H, W), (Hn, 8), (Hn, 4)],
+                                         [torch.uint8, torch.float32, torch.float64, torch.int32], p.device)
     if Hn:
         check(lib.fp_rasterize_extents(context(), mesh.handle, ptr(p), Hn, float(scale), float(fx), float(fy), float(cx), float(cy),
                                        int(W), int(H), ptr(rgb), ptr(depth), ptr(ext), ptr(boxes), current_stream()), "fp_rasterize_extents")
@@ -1154,6 +1168,30 @@ def gemm_plan(M: int, N: int, K: int, epi: int, ldx: Optional[int] = None, ldw: 
     kv = dict(f.split("=") for f in fields)
     return {"label": label, "row0": int(kv["row0"]), "ring": tuple(int(v) for v in kv["ring"].split(",")),
             "grid": tuple(int(v) for v in kv["grid"].split(",")), "text": text}
+
+
+def raster_plan(W: int, H: int, F: int, Hn: int, device: Optional[int] = None) -> dict:
+    """how rasterize() / rasterize_extents() would launch F triangles under Hn poses on a W x H frame, under the context's raster_tiled
+    (fp_op_raster_plan; nothing is launched): {"path": "tiled" | "global", "T": tile edge, "tiles": (ntx, nty), "chunks", "rounds", "bin":
+    bin workgroups per view, "views": (groups of 8, rest), "flush": "dword" | "bytes" | "none", "lds": bytes, "constants": {big_area,
+    big_tile_area, chunk, hits_round, small_span, max_tris, max_tile, clamp, znear: the thresholds the kernels were compiled with},
+    "text": the entry's own line}"""
+    import ctypes
+    buf = ctypes.create_string_buffer(384)
+    check(_lib.load().fp_op_raster_plan(context(device), int(W), int(H), int(F), int(Hn), buf, len(buf)), "fp_op_raster_plan")
+    return parse_raster_plan(buf.value.decode())
+
+
+def parse_raster_plan(text: str) -> dict:
+    """the dict of raster_plan() from the one-line text of fp_op_raster_plan / csrc/raster_plan.h plan_text"""
+    path, *fields = text.split()
+    kv = dict(f.split("=") for f in fields)
+    plan = {"path": path, "T": int(kv.pop("T")), "tiles": tuple(int(v) for v in kv.pop("tiles").split("x")), "chunks": int(kv.pop("chunks")),
+            "rounds": int(kv.pop("rounds")), "bin": int(kv.pop("bin")), "views": tuple(int(v) for v in kv.pop("views").split("+")),
+            "flush": kv.pop("flush"), "lds": int(kv.pop("lds"))}
+    plan["constants"] = {k: (float(v) if k == "znear" else int(v)) for k, v in kv.items()}
+    plan["text"] = text
+    return plan
 
 
 def workspace_read(name: str, shape, dtype=torch.bfloat16, device: Optional[int] = None) -> torch.Tensor:

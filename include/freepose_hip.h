@@ -332,6 +332,14 @@ int fp_op_workspace_read(fp_ctx* ctx, const char* name, void* host, size_t bytes
  * kernel in front); row0 = the first row of the second part (0 = no split), ring = K-tile ring depth of each part (0: not on the 64x64
  * tier), grid = workgroups of each part.  Host-only entry used by the tests of the tile tiers. */
 int fp_op_gemm_plan(fp_ctx* ctx, int M, int N, int K, int epi, int ldx, int ldw, int ln_part, char* out, size_t out_bytes);
+/* writes into `out` (at most out_bytes, NUL-terminated) how fp_rasterize / fp_rasterize_extents of this context would launch a mesh of F
+ * triangles under Hn poses on a W x H frame, under the context's "raster_tiled"; launches nothing.  The text is
+ *   <tiled|global> T=<tile edge> tiles=<ntx>x<nty> chunks=<n> rounds=<n> bin=<workgroups per view> views=<groups of 8>+<rest>
+ *   flush=<dword|bytes|none> lds=<bytes> big_area=.. big_tile_area=.. chunk=.. hits_round=.. small_span=.. max_tris=.. max_tile=..
+ *   clamp=.. znear=..
+ * (one line; tiles, chunks, rounds, bin and lds are 0 on the global path): the plan of csrc/raster_plan.h and the thresholds the kernels
+ * were compiled with.  Host-only entry used by the tests of the rasteriser's branches. */
+int fp_op_raster_plan(fp_ctx* ctx, int W, int H, int F, int Hn, char* out, size_t out_bytes);
 /* d_y[i] = bf16(0.5 x (1 + erf(x / sqrt 2))) elementwise on bf16 values in fp32: the direct expression the fc1 epilogue's GELU table
  * is filled from (hub DINOv2 Mlp act_layer = nn.GELU behind src/pipeline/retrieval/dino.py:18-19); the table-GELU GEMM is tested
  * against it on all 65 536 bf16 inputs */
