@@ -4,6 +4,16 @@
  * (void* = hipStream_t; NULL = default stream) and returns 0 on success or an FP_ERR_* code, with
  * fp_last_error() giving the text.  No exceptions cross this boundary.  Nothing here touches torch.
  *
+ * Streams.  ALL device work of a call — kernels, memsets, copies, weight repacks — is enqueued on the stream the call is given, and a call
+ * returns without waiting unless its comment says that it synchronises that stream (fp_geodesic_select, fp_gt_visibility,
+ * fp_pts_diameter, fp_video_errors, fp_clip_text_encode).  Nothing on the steady path waits for the whole device: the only device-wide
+ * waits are one-off (the GELU table of a device, the re-fold after a ViT weight was replaced), and a workspace is freed — which drains the
+ * device — only when a call needs it larger than any call before.  Calls on one context are ordered by the caller: a context is "one
+ * context per thread/GPU, no locking", its workspaces (and those of the ViT / CLIP / mesh handles made on it) are shared by all of its
+ * calls, so two streams may use a context only with an event or wait between their calls (hipStreamWaitEvent, or a host wait); state a
+ * call builds on its stream — folded weights, resized position rows, repacked patch weights, the FFA arrival counters, a workspace's
+ * first allocation — is then safe to use from the other stream.  tests/test_gpu_streams.py holds every entry to this.
+ *
  * Each entry names the reference interface it replaces (file:line relative to ponimatkin/freepose).
  * bf16 tensors are raw uint16 bit patterns.
  */
