@@ -45,13 +45,32 @@
 //   pyrender's fragment shader is third-party and absent from /root/reference: the shading rule is STATED here, not pinned
 //   (DESIGN.md §5).  A GPU derives the level of detail from 2x2-quad finite differences with a few fractional bits; the analytic
 //   derivative used here is the quantity those approximate.
-// Launch shape: vertex kernel (Hn x V threads), triangle kernel (Hn x F threads; small triangles are
-// rasterised by their thread, large ones by a whole wave via a queue), resolve kernel (Hn x pixels).
+// Launch shape (the plan is fp_raster::make_plan, raster_plan.h; the arithmetic above is raster_core.h): vertex kernel (Hn x V threads), then
+//   tiled (frames up to 704 px, up to 131 072 triangles): bin kernel (one wave per chunk of 64 Morton-ordered triangles: tile boxes and chunk
+//     masks), tile kernel (one workgroup per view and screen tile: visibility keys in LDS, resolve and flush in place, one extents record),
+//     extents kernel (one wave per view folds the records) when boxes / extents are asked for;
+//   global buffer (everything else): triangle kernel (Hn x F threads; small triangles are rasterised by their thread, large ones and
+//     straddlers by a whole wave of the big kernel via a queue), resolve kernel (Hn x pixels), fp_depth_extents on the depth image.
 #include "../../include/freepose_hip.h"
 #include "internal.h"
 #include "raster_plan.h"   // the launch arithmetic and every threshold the kernels branch on, stated once (checked on a CPU)
+#include "raster_core.h"   // the per-vertex and per-triangle arithmetic, stated once for host and device (checked on a CPU)
 
 #include <algorithm>
+#include <memory>
+
+// what shading reads of a mesh, as the kernels take it (shade_fragment; arithmetic = the contract above)
+struct ShadeArgs {
+    const uint8_t* colors = nullptr;   // [V,4] rgba (a unused), by device vertex id; null: white
+    const float* uv = nullptr;         // [F,3,2] per-corner texture coordinates (textured meshes)
+    const uint8_t* tex = nullptr;      // rgba diffuse texture, all mip levels back to back (level k at texel offset lev_off[k])
+    int th = 0, tw = 0;
+    float kd0 = 1.f, kd1 = 1.f, kd2 = 1.f;   // material diffuse factor (MTL Kd / glTF baseColorFactor)
+    float ambient = 2.0f;              // scene ambient light factor: 2 in renderer.py:53-55, 5 in tracking_refiner.py:33
+    int shade = 1;                     // 1 = gamma rule, 0 = linear
+    int nlev = 0, filter = 1;          // mip levels; 1 = trilinear mip-maps, 0 = bilinear level 0
+    uint32_t lev_off[16] = {};
+};
 
 struct fp_mesh {
     fp_ctx* ctx = nullptr;
@@ -61,252 +80,80 @@ struct fp_mesh {
     int32_t* fsort = nullptr;  // [F,3] faces[perm[slot]]: the corner ids in slot order (read coalesced by the bin / tile kernels)
     std::vector<int32_t> h_vmap;   // host copy of vmap (per-vertex attributes are stored by device id)
     int32_t* vmap = nullptr;   // [V] caller's vertex id -> device vertex id (vertices are stored in order of first use by the Morton-sorted
-                               // triangles, so the 3 x 64 vertex gathers of a chunk hit a few cache lines instead of one line each)
-    uint8_t* colors = nullptr; // [V,4] rgba (a unused)
-    float* uv = nullptr;       // [F,3,2] per-corner texture coordinates (textured meshes)
-    uint8_t* tex = nullptr;    // rgba diffuse texture, all mip levels back to back (level k at texel offset lev_off[k])
-    int nlev = 0;
-    uint32_t lev_off[16] = {};
-    int filter = 1;            // 1 = trilinear mip-maps, 0 = bilinear level 0
+                               // triangles, so the 3 x 64 vertex gathers of a chunk hit a few cache lines instead of one line each).  Purely
+                               // internal: outputs carry no vertex id, fp_project_vertices maps back
+    ShadeArgs sh;              // colours or texture, material, shading rule
     int cull = 0;              // 1 = back faces are not drawn (renderer.py:63-66: render without SKIP_CULL_FACES), 0 = both sides
     float* tables = nullptr;   // DEC[256] sRGB->linear, THR[256] gamma-encode thresholds
-    int th = 0, tw = 0;
-    float kd[3] = {1.f, 1.f, 1.f};   // material diffuse factor (MTL Kd / glTF baseColorFactor)
-    int shade = 1;             // 1 = gamma rule, 0 = linear (see the contract above)
     int V = 0, F = 0;
-    float ambient = 2.0f;      // scene ambient light factor: 2 in renderer.py:53-55, 5 in tracking_refiner.py:33
 };
 
 namespace {
 
-struct SVert { int xi, yi; float iz, zc; };
-struct RasterView { float R[9]; float t[3]; };
-
-using fp_raster::ZNEAR;
-using fp_raster::BIG_AREA;     // bbox pixels above which a triangle goes to the wave-per-triangle queue
-using fp_raster::CLAMP_PX;
-using fp_raster::SMALL_SPAN;
+using namespace fp_raster;     // raster_core.h: SVert, TriSetup, EdgeFn, barycentrics, visibility key, Strad; raster_plan.h: the thresholds
 
 __global__ void raster_vertex_kernel(const float* __restrict__ verts, int V, const float* __restrict__ poses, int Hn,
                                      float scale, float fx, float fy, float cx, float cy, SVert* __restrict__ sv) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int h = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, h = blockIdx.y;
     if (i >= V) return;
-    const float* P = poses + (size_t)h * 16;
-    const float sx = scale * verts[3 * i], sy = scale * verts[3 * i + 1], sz = scale * verts[3 * i + 2];
-    const float Xc = fmaf(P[0], sx, fmaf(P[1], sy, fmaf(P[2], sz, P[3])));
-    const float Yc = fmaf(P[4], sx, fmaf(P[5], sy, fmaf(P[6], sz, P[7])));
-    const float Zc = fmaf(P[8], sx, fmaf(P[9], sy, fmaf(P[10], sz, P[11])));
-    SVert o;
-    o.zc = Zc;
-    if (Zc > ZNEAR) {
-        const float iz = 1.0f / Zc;
-        const float u = fmaf(fx, Xc * iz, cx), v = fmaf(fy, Yc * iz, cy);
-        // clamp far-off-screen coordinates so the fixed-point products stay inside int64
-        const float uc = fminf(fmaxf(u, -CLAMP_PX), CLAMP_PX), vc = fminf(fmaxf(v, -CLAMP_PX), CLAMP_PX);
-        o.xi = (int)rintf(uc * 256.0f);
-        o.yi = (int)rintf(vc * 256.0f);
-        o.iz = iz;
-    } else {   // behind the near plane: homogeneous pixel coordinates for straddling triangles (contract in the header)
-        o.xi = (int)__float_as_uint(fmaf(fx, Xc, cx * Zc));
-        o.yi = (int)__float_as_uint(fmaf(fy, Yc, cy * Zc));
-        o.iz = 0.f;
-    }
-    sv[(size_t)h * V + i] = o;
+    sv[(size_t)h * V + i] = project_vertex(poses + (size_t)h * 16, verts[3 * i], verts[3 * i + 1], verts[3 * i + 2], scale, fx, fy, cx, cy);
 }
 
-struct TriSetup {
-    int x0, y0, x1, y1, x2, y2;
-    float iz0, iz1, iz2;
-    long long area2;
-    int bx0, by0, bx1, by1;  // pixel bbox, inclusive, clipped
-    int i0, i1, i2;          // vertex ids after orientation normalisation
-    bool ok;
-    bool swapped;            // corners 1 and 2 were exchanged (per-corner attributes follow)
-    bool strad;              // straddles the near plane: homogeneous rasterisation over the whole frame (struct Strad)
-    bool small;              // spans < 128 px in x and y: every edge function at a candidate pixel fits 32 bits (tri_cover32)
-};
-
-// homogeneous edge functions of a triangle that straddles the near plane (contract in the header)
-struct Strad { double a[3], b[3], c[3], det; };
-__device__ __forceinline__ void strad_vertex(const SVert& v, double& x, double& y, double& w) {
-    w = (double)v.zc;
-    if (v.zc > ZNEAR) {
-        x = ((double)v.xi * (1.0 / 256.0)) * w;
-        y = ((double)v.yi * (1.0 / 256.0)) * w;
-    } else {
-        x = (double)__uint_as_float((unsigned)v.xi);
-        y = (double)__uint_as_float((unsigned)v.yi);
-    }
-}
-__device__ __forceinline__ Strad strad_setup(const SVert* __restrict__ sv, const int32_t* __restrict__ faces, int f) {
-    double x[3], y[3], w[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) strad_vertex(sv[faces[3 * f + k]], x[k], y[k], w[k]);
-    Strad q;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
-        q.a[k] = y[k1] * w[k2] - y[k2] * w[k1];
-        q.b[k] = x[k2] * w[k1] - x[k1] * w[k2];
-        q.c[k] = x[k1] * y[k2] - x[k2] * y[k1];
-    }
-    q.det = (x[0] * q.a[0] + y[0] * q.b[0]) + w[0] * q.c[0];
-    return q;
-}
-// coverage, depth and perspective-correct barycentrics of pixel (px, py)
-__device__ __forceinline__ bool strad_pixel(const Strad& q, int px, int py, float& d, float& b0, float& b1, float& b2) {
-    const double X = (double)px + 0.5, Y = (double)py + 0.5;
-    double e0 = (q.a[0] * X + q.b[0] * Y) + q.c[0];
-    double e1 = (q.a[1] * X + q.b[1] * Y) + q.c[1];
-    double e2 = (q.a[2] * X + q.b[2] * Y) + q.c[2];
-    double det = q.det;
-    if (det < 0.0) { e0 = -e0; e1 = -e1; e2 = -e2; det = -det; }
-    if (!(det > 0.0) || e0 < 0.0 || e1 < 0.0 || e2 < 0.0) return false;
-    const double S = (e0 + e1) + e2;
-    if (!(S > 0.0)) return false;
-    const double z = det / S;
-    if (!(z > (double)ZNEAR)) return false;
-    d = (float)z;
-    b0 = (float)(e0 / S); b1 = (float)(e1 / S); b2 = (float)(e2 / S);
-    return true;
-}
-
-__device__ __forceinline__ bool topleft(int dx, int dy) { return (dy < 0) || (dy == 0 && dx > 0); }
-
-// set-up from the three screen-space vertices already in registers (callers that batch their gathers load them first)
-__device__ __forceinline__ TriSetup tri_setup_v(SVert a, SVert b, SVert c, int i0, int i1, int i2, int W, int Hh) {
-    TriSetup t;
-    const int nfront = (a.zc > ZNEAR) + (b.zc > ZNEAR) + (c.zc > ZNEAR);
-    t.ok = nfront == 3;
-    t.strad = nfront == 1 || nfront == 2;
-    if (t.strad) {   // near-plane straddler: candidate pixels = the whole frame, original corner order, no fixed-point set-up
-        t.ok = true; t.swapped = false; t.area2 = 1; t.small = false;
-        t.x0 = t.y0 = t.x1 = t.y1 = t.x2 = t.y2 = 0;
-        t.iz0 = t.iz1 = t.iz2 = 0.f;
-        t.i0 = i0; t.i1 = i1; t.i2 = i2;
-        t.bx0 = 0; t.by0 = 0; t.bx1 = W - 1; t.by1 = Hh - 1;
-        return t;
-    }
-    long long area2 = (long long)(b.xi - a.xi) * (c.yi - a.yi) - (long long)(b.yi - a.yi) * (c.xi - a.xi);
-    t.swapped = area2 < 0;
-    if (area2 < 0) {
-        SVert tmp = b; b = c; c = tmp;
-        int ti = i1; i1 = i2; i2 = ti;
-        area2 = -area2;
-    }
-    t.area2 = area2;
-    if (area2 == 0) t.ok = false;
-    t.x0 = a.xi; t.y0 = a.yi; t.x1 = b.xi; t.y1 = b.yi; t.x2 = c.xi; t.y2 = c.yi;
-    t.iz0 = a.iz; t.iz1 = b.iz; t.iz2 = c.iz;
-    t.i0 = i0; t.i1 = i1; t.i2 = i2;
-    const int mnx = min(a.xi, min(b.xi, c.xi)), mxx = max(a.xi, max(b.xi, c.xi));
-    const int mny = min(a.yi, min(b.yi, c.yi)), mxy = max(a.yi, max(b.yi, c.yi));
-    // pixel p is a candidate when its centre 256p+128 lies in [mn, mx]
-    t.bx0 = max(0, (mnx - 128 + 255) >> 8);
-    t.by0 = max(0, (mny - 128 + 255) >> 8);
-    t.bx1 = min(W - 1, (mxx - 128) >> 8);
-    t.by1 = min(Hh - 1, (mxy - 128) >> 8);
-    if (t.bx1 < t.bx0 || t.by1 < t.by0) t.ok = false;
-    t.small = (mxx - mnx) < SMALL_SPAN && (mxy - mny) < SMALL_SPAN;
-    return t;
-}
-__device__ __forceinline__ TriSetup tri_setup(const SVert* __restrict__ sv, const int32_t* __restrict__ faces, int f,
-                                              int W, int Hh) {
+__device__ __forceinline__ TriSetup tri_setup(const SVert* __restrict__ sv, const int32_t* __restrict__ faces, int f, int W, int Hh) {
     const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-    return tri_setup_v(sv[i0], sv[i1], sv[i2], i0, i1, i2, W, Hh);
+    return tri_setup_v(sv[i0], sv[i1], sv[i2], W, Hh);
 }
 
-// edge functions at the pixel centre; returns coverage and the three (non-negative) weights
-__device__ __forceinline__ bool tri_cover(const TriSetup& t, int px, int py, long long& w0, long long& w1, long long& w2) {
-    const long long sx = (long long)px * 256 + 128, sy = (long long)py * 256 + 128;
-    // E_ab(p) = (bx-ax)(py-ay) - (by-ay)(px-ax); positive inside for area2 > 0
-    w0 = (long long)(t.x2 - t.x1) * (sy - t.y1) - (long long)(t.y2 - t.y1) * (sx - t.x1);  // opposite v0
-    w1 = (long long)(t.x0 - t.x2) * (sy - t.y2) - (long long)(t.y0 - t.y2) * (sx - t.x2);  // opposite v1
-    w2 = (long long)(t.x1 - t.x0) * (sy - t.y0) - (long long)(t.y1 - t.y0) * (sx - t.x0);  // opposite v2
-    if (w0 < 0 || w1 < 0 || w2 < 0) return false;
-    if (w0 == 0 && !topleft(t.x2 - t.x1, t.y2 - t.y1)) return false;
-    if (w1 == 0 && !topleft(t.x0 - t.x2, t.y0 - t.y2)) return false;
-    if (w2 == 0 && !topleft(t.x1 - t.x0, t.y1 - t.y0)) return false;
-    return true;
+// ---- where a fragment's visibility key goes.  NARROW: the sink's small triangles take the 32-bit edge functions (fragment<NARROW>)
+struct GlobalSink {   // the global visibility buffer of one view
+    static constexpr bool NARROW = false;
+    unsigned long long* __restrict__ zb;   // [Hh, W]
+    int W;
+    __device__ __forceinline__ void put(int px, int py, unsigned long long key) const {
+        // (a read-before-atomic "cannot win" test was measured here: the scattered 8-byte loads cost more than the L2 atomics
+        //  they save — 2.4 -> 3.5 ms per 576 views — so the atomic is issued unconditionally)
+        atomicMin(&zb[(size_t)py * W + px], key);
+    }
+};
+// the tiled path's sink, and what the stages of raster_tile_kernel share: this workgroup's tile, its dynamic LDS, the view's vertices
+struct TileCtx {
+    static constexpr bool NARROW = true;
+    int h, tx, ty, W, Hh;           // view, tile coordinates, frame
+    int X0, Y0, X1, Y1, T;          // the tile's pixels (inclusive, clipped to the frame) and the tile edge = LDS row pitch
+    unsigned long long* tile;       // [T*T] visibility keys; after resolve_tile depth bits << 32 | b << 16 | g << 8 | r
+    float* tab;                     // DEC / THR tables (512 floats)
+    unsigned short* hits;           // [HITS_ROUND] chunks of the round that touch the tile, relative to the round's base
+    double *ax, *ay;                // [T] each: (pixel - c) / f of the tile's columns / rows
+    const SVert* sv;                // the view's vertices; below: the mesh's faces by device vertex id
+    const int32_t* faces;
+    int lane, wave;
+    __device__ __forceinline__ int tw() const { return X1 - X0 + 1; }
+    __device__ __forceinline__ int th() const { return Y1 - Y0 + 1; }
+    __device__ __forceinline__ void put(int px, int py, unsigned long long key) const {
+        unsigned long long* slot = &tile[(py - Y0) * T + (px - X0)];
+        // stored keys only ever decrease, so a plain (possibly stale) read bounds the current value from above: a key that does
+        // not beat it cannot change the slot (LDS reads are cheap; the same test on the global buffer is a loss, see GlobalSink)
+        if (key >= *(volatile unsigned long long*)slot) return;
+        atomicMin(slot, key);
+    }
+};
+// the one fragment emitter: triangle f, set up as `g` (TriSetup or Strad), at pixel (px, py)
+template <class Geom, class Sink> __device__ __forceinline__ void emit(const Geom& g, int f, int px, int py, const Sink& s) {
+    float d;
+    if (fragment<Sink::NARROW>(g, px, py, d)) s.put(px, py, vis_key(d, f));
 }
-
-// The same edge functions for a `small` triangle at one of its candidate pixels (centre inside the vertex bounding box): every
-// difference is below 2^15 in magnitude, so the products fit 24 x 24 -> 32-bit multiplies (v_mul_i32_i24, full rate; a 64-bit product
-// is four quarter-rate multiplies) and the sums 32 bits: the SAME integers as tri_cover, hence the same coverage, the same float
-// conversions and the same depth bits — what the dense meshes' ~1-pixel triangles spend their time on.
-__device__ __forceinline__ bool tri_cover32(const TriSetup& t, int px, int py, int& w0, int& w1, int& w2) {
-    const int sx = px * 256 + 128, sy = py * 256 + 128;
-    w0 = __mul24(t.x2 - t.x1, sy - t.y1) - __mul24(t.y2 - t.y1, sx - t.x1);
-    w1 = __mul24(t.x0 - t.x2, sy - t.y2) - __mul24(t.y0 - t.y2, sx - t.x2);
-    w2 = __mul24(t.x1 - t.x0, sy - t.y0) - __mul24(t.y1 - t.y0, sx - t.x0);
-    if ((w0 | w1 | w2) < 0) return false;
-    if (w0 == 0 && !topleft(t.x2 - t.x1, t.y2 - t.y1)) return false;
-    if (w1 == 0 && !topleft(t.x0 - t.x2, t.y0 - t.y2)) return false;
-    if (w2 == 0 && !topleft(t.x1 - t.x0, t.y1 - t.y0)) return false;
-    return true;
-}
-// b_i = float(w_i) / float(area2), the IEEE quotient, WITHOUT its ~12-instruction expansion per weight: the reciprocal of the area is
-// taken once per triangle in double (rd = RN(1 / fa)), each weight is then one fp64 multiply rounded to float.  The double product is
-// within 2^-52 (relative) of the exact quotient; a quotient of two 24-bit significands is never closer than 2^-49 to a rounding
-// midpoint of the float grid (|x/n - m| >= 1 / (N k) for a 25-bit midpoint significand k), so rounding the product gives the
-// correctly rounded quotient: the bits of the division (and of the oracle).
-__device__ __forceinline__ double tri_rcp_area(const TriSetup& t) { return 1.0 / (double)(float)(int)t.area2; }
-__device__ __forceinline__ float tri_depth32(const TriSetup& t, double rd, int w0, int w1, int w2, float& b0, float& b1, float& b2) {
-    b0 = (float)((double)(float)w0 * rd); b1 = (float)((double)(float)w1 * rd); b2 = (float)((double)(float)w2 * rd);
-    const float izp = fmaf(b2, t.iz2, fmaf(b1, t.iz1, b0 * t.iz0));
-    return 1.0f / izp;
-}
-
-__device__ __forceinline__ float tri_depth(const TriSetup& t, long long w0, long long w1, long long w2, float& b0,
-                                           float& b1, float& b2) {
-    const float fa = (float)t.area2;
-    b0 = (float)w0 / fa; b1 = (float)w1 / fa; b2 = (float)w2 / fa;
-    const float izp = fmaf(b2, t.iz2, fmaf(b1, t.iz1, b0 * t.iz0));
-    return 1.0f / izp;
-}
-
-__device__ __forceinline__ void tri_pixel(const TriSetup& t, int f, int px, int py, unsigned long long* __restrict__ zb,
-                                          int W) {
-    long long w0, w1, w2;
-    if (!tri_cover(t, px, py, w0, w1, w2)) return;
-    float b0, b1, b2;
-    const float d = tri_depth(t, w0, w1, w2, b0, b1, b2);
-    if (!(d > 0.f)) return;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)f;
-    // (a read-before-atomic "cannot win" test was measured here: the scattered 8-byte loads cost more than the L2 atomics
-    //  they save — 2.4 -> 3.5 ms per 576 views — so the atomic is issued unconditionally)
-    atomicMin(&zb[(size_t)py * W + px], key);
-}
-
-// Back face (renderer.py:63-66, cull_faces = True -> GL_CULL_FACE with counter-clockwise front faces): in this frame (x right, y down,
-// z forward) a counter-clockwise-from-outside triangle that faces the camera has a NEGATIVE screen-space area, i.e. tri_setup swapped
-// its corners; a straddler is classified by the sign of its homogeneous determinant (same sign as the area when all w > 0).
-__device__ __forceinline__ bool back_facing(const TriSetup& t, const SVert* __restrict__ sv, const int32_t* __restrict__ faces, int f) {
-    if (t.strad) return strad_setup(sv, faces, f).det > 0.0;
-    return !t.swapped;
-}
-
-__device__ __forceinline__ void strad_pixel_global(const Strad& q, int f, int px, int py, unsigned long long* __restrict__ zb, int W) {
-    float d, b0, b1, b2;
-    if (!strad_pixel(q, px, py, d, b0, b1, b2)) return;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)f;
-    atomicMin(&zb[(size_t)py * W + px], key);
+// a whole wave on one triangle: the lanes stride over the np pixels of a box bw wide from (x0, y0); near-plane straddlers by their own form
+template <class Sink> __device__ __forceinline__ void wave_rasterize(const TriSetup& t, const SVert* __restrict__ sv, const int32_t* __restrict__ faces,
+                                                                     int f, int x0, int y0, int bw, int np, int lane, const Sink& s) {
+    if (t.strad) {   // wave-uniform
+        const Strad sq = strad_setup(sv, faces, f);
+        for (int j = lane; j < np; j += 64) emit(sq, f, x0 + j % bw, y0 + j / bw, s);
+        return;
+    }
+    for (int j = lane; j < np; j += 64) emit(t, f, x0 + j % bw, y0 + j / bw, s);
 }
 
 // ---- shading of the visible fragment (shared by both visibility strategies; arithmetic = the contract in the header) ----
-struct ShadeArgs {
-    const uint8_t* colors;   // [V,4] or null
-    const float* uv;         // [F,3,2] or null
-    const uint8_t* tex;      // rgba mip chain or null
-    int th, tw;
-    float kd0, kd1, kd2;
-    float ambient;
-    int shade;
-    int nlev, filter;
-    uint32_t lev_off[16];
-};
-
 // largest k in [0,255] with thr[k] <= x (thr[0] = 0); the pow() estimate only decides how many table steps are taken
 __device__ __forceinline__ uint8_t encode_gamma(float x, const float* thr) {
     if (!(x > 0.f)) return 0;
@@ -438,17 +285,16 @@ __device__ __forceinline__ void shade_fragment(const ShadeArgs& s, const TriSetu
 
 // resolve one pixel whose visibility key is `key`: depth and colour of the winning triangle.  `t` / `at`: the winner's set-up and
 // attributes (loaded by the caller; ignored for a background pixel)
-__device__ __forceinline__ void resolve_pixel_v(const SVert* __restrict__ sv, const int32_t* __restrict__ faces, const ShadeArgs& s,
+template <bool NARROW> __device__ __forceinline__ void resolve_pixel_v(const SVert* __restrict__ sv, const int32_t* __restrict__ faces, const ShadeArgs& s,
                                                 const float* tab, unsigned long long key, const TriSetup& t, const TriAttr& at, int px,
                                                 int py, float& d, uint8_t (&out)[3]) {
     d = 0.f;
     out[0] = out[1] = out[2] = 0;
-    if (key == ~0ull) return;
-    const int f = (int)(unsigned)(key & 0xffffffffu);
-    d = __uint_as_float((unsigned)(key >> 32));
+    if (key == KEY_NONE) return;
+    d = key_depth(key);
     float b0, b1, b2;
     if (t.strad) {   // near-plane straddler: true (3-D) barycentrics, level-0 texture
-        const Strad q = strad_setup(sv, faces, f);
+        const Strad q = strad_setup(sv, faces, key_face(key));
         float ds;
         strad_pixel(q, px, py, ds, b0, b1, b2);
         shade_fragment(s, t, at, b0, b1, b2, 1.0f, tab, out, true);
@@ -456,39 +302,29 @@ __device__ __forceinline__ void resolve_pixel_v(const SVert* __restrict__ sv, co
     }
     // the winner's weights again (three IEEE quotients: per PIXEL that is cheaper than the fp64 reciprocal the raster pass amortises
     // over a triangle); its depth is the key's — the same bits the raster pass computed from the same weights
-    const float fa = (float)t.area2;
-    if (t.small) {
-        int w0, w1, w2;
-        tri_cover32(t, px, py, w0, w1, w2);
-        b0 = (float)w0 / fa; b1 = (float)w1 / fa; b2 = (float)w2 / fa;
-    } else {
-        long long w0, w1, w2;
-        tri_cover(t, px, py, w0, w1, w2);
-        b0 = (float)w0 / fa; b1 = (float)w1 / fa; b2 = (float)w2 / fa;
-    }
+    if (t.small) { int w0, w1, w2; cover_at<NARROW, int>(t, px, py, w0, w1, w2); bary3(t, w0, w1, w2, b0, b1, b2); }
+    else { long long w0, w1, w2; cover_at<NARROW, long long>(t, px, py, w0, w1, w2); bary3(t, w0, w1, w2, b0, b1, b2); }
     shade_fragment(s, t, at, b0 * t.iz0, b1 * t.iz1, b2 * t.iz2, d, tab, out);
 }
 __device__ __forceinline__ void resolve_pixel(const SVert* __restrict__ sv, const int32_t* __restrict__ faces, const ShadeArgs& s,
-                                              const float* tab, unsigned long long key, int px, int py, int W, int Hh, float& d,
-                                              uint8_t (&out)[3]) {
-    if (key == ~0ull) { d = 0.f; out[0] = out[1] = out[2] = 0; return; }
-    const int f = (int)(unsigned)(key & 0xffffffffu);
+                                              const float* tab, unsigned long long key, int px, int py, int W, int Hh, float& d, uint8_t (&out)[3]) {
+    if (key == KEY_NONE) { d = 0.f; out[0] = out[1] = out[2] = 0; return; }
+    const int f = key_face(key);
     const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
     const TriAttr at = load_attr(s, f, i0, i1, i2);
-    const TriSetup t = tri_setup_v(sv[i0], sv[i1], sv[i2], i0, i1, i2, W, Hh);
-    resolve_pixel_v(sv, faces, s, tab, key, t, at, px, py, d, out);
+    const TriSetup t = tri_setup_v(sv[i0], sv[i1], sv[i2], W, Hh);
+    resolve_pixel_v<GlobalSink::NARROW>(sv, faces, s, tab, key, t, at, px, py, d, out);
 }
 
 __global__ __launch_bounds__(256) void raster_tri_kernel(const SVert* __restrict__ sv_all, const int32_t* __restrict__ faces,
-                                                         const int32_t* __restrict__ perm, int V, int F, int W, int Hh,
-                                                         unsigned long long* __restrict__ zb_all,
+                                                         const int32_t* __restrict__ perm, int V, int F, int W, int Hh, unsigned long long* __restrict__ zb_all,
                                                          int* __restrict__ queue, int* __restrict__ qcount, int qcap, int cull) {
     const int slot = blockIdx.x * blockDim.x + threadIdx.x;
     const int h = blockIdx.y;
     if (slot >= F) return;
     const int f = perm[slot];     // Morton order of the centroids: a wave's 64 triangles (and their atomics) are neighbours on the screen whatever the file's face order
     const SVert* sv = sv_all + (size_t)h * V;
-    unsigned long long* zb = zb_all + (size_t)h * W * Hh;
+    const GlobalSink zb{zb_all + (size_t)h * W * Hh, W};
     const TriSetup t = tri_setup(sv, faces, f, W, Hh);
     if (!t.ok) return;
     if (cull && back_facing(t, sv, faces, f)) return;
@@ -501,18 +337,17 @@ __global__ __launch_bounds__(256) void raster_tri_kernel(const SVert* __restrict
     if (t.strad) {
         const Strad q = strad_setup(sv, faces, f);
         for (int py = 0; py < Hh; ++py)
-            for (int px = 0; px < W; ++px) strad_pixel_global(q, f, px, py, zb, W);
+            for (int px = 0; px < W; ++px) emit(q, f, px, py, zb);
         return;
     }
     for (int py = t.by0; py <= t.by1; ++py)
-        for (int px = t.bx0; px <= t.bx1; ++px) tri_pixel(t, f, px, py, zb, W);
+        for (int px = t.bx0; px <= t.bx1; ++px) emit(t, f, px, py, zb);
 }
 
 // one wave per queued (view, triangle): lanes stride over the bbox pixels
 __global__ __launch_bounds__(256) void raster_big_kernel(const SVert* __restrict__ sv_all, const int32_t* __restrict__ faces,
                                                          int V, int W, int Hh, unsigned long long* __restrict__ zb_all,
-                                                         const int* __restrict__ queue, const int* __restrict__ qcount,
-                                                         int qcap) {
+                                                         const int* __restrict__ queue, const int* __restrict__ qcount, int qcap) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwave = (gridDim.x * blockDim.x) >> 6;
@@ -520,21 +355,13 @@ __global__ __launch_bounds__(256) void raster_big_kernel(const SVert* __restrict
     for (int q = wave; q < n; q += nwave) {
         const int h = queue[2 * q], f = queue[2 * q + 1];
         const TriSetup t = tri_setup(sv_all + (size_t)h * V, faces, f, W, Hh);
-        unsigned long long* zb = zb_all + (size_t)h * W * Hh;
-        const int bw = t.bx1 - t.bx0 + 1, bh = t.by1 - t.by0 + 1;
-        if (t.strad) {   // wave-uniform
-            const Strad sq = strad_setup(sv_all + (size_t)h * V, faces, f);
-            for (int i = lane; i < bw * bh; i += 64) strad_pixel_global(sq, f, i % bw, i / bw, zb, W);
-            continue;
-        }
-        for (int i = lane; i < bw * bh; i += 64) tri_pixel(t, f, t.bx0 + i % bw, t.by0 + i / bw, zb, W);
+        const int bw = t.bx1 - t.bx0 + 1, bh = t.by1 - t.by0 + 1;   // (a straddler's box is the frame)
+        wave_rasterize(t, sv_all + (size_t)h * V, faces, f, t.bx0, t.by0, bw, bw * bh, lane, GlobalSink{zb_all + (size_t)h * W * Hh, W});
     }
 }
 
-__global__ __launch_bounds__(256) void raster_resolve_kernel(const SVert* __restrict__ sv_all,
-                                                             const int32_t* __restrict__ faces, ShadeArgs sh,
-                                                             const float* __restrict__ tables, int V, int W, int Hh,
-                                                             const unsigned long long* __restrict__ zb_all,
+__global__ __launch_bounds__(256) void raster_resolve_kernel(const SVert* __restrict__ sv_all, const int32_t* __restrict__ faces, ShadeArgs sh,
+                                                             const float* __restrict__ tables, int V, int W, int Hh, const unsigned long long* __restrict__ zb_all,
                                                              uint8_t* __restrict__ rgb, float* __restrict__ depth) {
     __shared__ float tab[512];
     tab[threadIdx.x] = tables[threadIdx.x];
@@ -572,37 +399,19 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const SVert* __rest
 //                 (count, pixel bbox, fp64 cloud extents: min / max / integer sums, order-independent, hence bit-identical) to one
 //                 partial record per tile; raster_extents_kernel folds the <= 64 records of a view.  The depth image itself is
 //                 optional: the pose hot path needs only the extents (pose_estimator.py:104-112) and the crops.
-// Same tri_setup / tri_cover / tri_depth, same candidate pixel set (bbox ∩ tile over all tiles = bbox), same 64-bit key and
+// Same tri_setup_v / EdgeFn / barycentrics, same candidate pixel set (bbox ∩ tile over all tiles = bbox), same 64-bit key and
 // an order-independent minimum: the output is bit-identical to the global-buffer path and to the oracle.
-using fp_raster::BIN_CHUNK;
-using fp_raster::BIG_TILE_AREA;          // candidate pixels in the tile above which a triangle is handed to the whole wave
-using fp_raster::HITS_ROUND;             // chunk masks examined per round of the tile kernel (8 per thread; 16-bit ids relative to the round's base)
-static_assert(fp_raster::BIN_WAVES * 64 == 256 && fp_raster::TILE_THREADS == 256 && HITS_ROUND % fp_raster::TILE_THREADS == 0 &&
-                  HITS_ROUND <= 65536 && BIG_TILE_AREA <= 32 && BIN_CHUNK == 64 && 2 * fp_raster::TILE_MAX <= fp_raster::TILE_THREADS &&
-                  fp_raster::TILES_SIDE == 8 && fp_raster::tile_lds(fp_raster::TILE_MAX) <= (size_t)fp_raster::LDS_BUDGET,
+static_assert(BIN_WAVES * 64 == 256 && TILE_THREADS == 256 && HITS_ROUND % TILE_THREADS == 0 && HITS_ROUND <= 65536 && BIG_TILE_AREA <= 32 &&
+                  BIN_CHUNK == 64 && 2 * TILE_MAX <= TILE_THREADS && TILES_SIDE == 8 && tile_lds(TILE_MAX) <= (size_t)LDS_BUDGET,
               "raster_plan.h describes other kernels");
 constexpr uint16_t TBOX_NONE = 0x000f;   // tx0 = 15 > tx1 = 0: overlaps nothing
 constexpr int PART_N = 10;               // doubles per (view, tile) extents record
 
-// Workgroup -> (item, view) with all items of a view on ONE XCD: workgroup L of a launch runs on XCD L % 8 (observed; a speed hint
-// only, MI355X_MICROARCH.md "Workgroup dispatch"), so within a group of 8 views the linear id walks the views fastest.
-__device__ __forceinline__ void view_major_ids(int nx, int Hn, int& item, int& h) {
-    fp_raster::view_major(blockIdx.y * nx + blockIdx.x, nx, Hn, item, h);   // (stated in raster_plan.h: the host check walks it over whole grids)
-}
-
-__device__ __forceinline__ unsigned long long wave_or64(unsigned long long m) {
-    unsigned lo = (unsigned)m, hi = (unsigned)(m >> 32);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { lo |= __shfl_xor(lo, off, 64); hi |= __shfl_xor(hi, off, 64); }
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__global__ __launch_bounds__(256) void raster_bin_kernel(const SVert* __restrict__ sv_all, const int32_t* __restrict__ faces,
-                                                         const int32_t* __restrict__ perm, const int32_t* __restrict__ fsort, int V,
-                                                         int F, int W, int Hh, int T, int Hn, int nchunk,
-                                                         uint16_t* __restrict__ tbox, unsigned long long* __restrict__ cmask, int cull) {
+__global__ __launch_bounds__(256) void raster_bin_kernel(
+    const SVert* __restrict__ sv_all, const int32_t* __restrict__ faces, const int32_t* __restrict__ perm, const int32_t* __restrict__ fsort, int V, int F,
+    int W, int Hh, int T, int Hn, int nchunk, uint16_t* __restrict__ tbox, unsigned long long* __restrict__ cmask, int cull) {
     int item, h;
-    view_major_ids(gridDim.x, Hn, item, h);
+    view_major(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, Hn, item, h);   // all items of a view on one XCD (raster_plan.h)
     const int lane = threadIdx.x & 63;
     const int chunk = item * 4 + (threadIdx.x >> 6);
     if (chunk >= nchunk) return;                         // wave-uniform
@@ -612,7 +421,7 @@ __global__ __launch_bounds__(256) void raster_bin_kernel(const SVert* __restrict
     if (slot < F) {
         const SVert* sv = sv_all + (size_t)h * V;
         const int i0 = fsort[3 * slot], i1 = fsort[3 * slot + 1], i2 = fsort[3 * slot + 2];   // the slot's corners, read in slot order
-        const TriSetup t = tri_setup_v(sv[i0], sv[i1], sv[i2], i0, i1, i2, W, Hh);
+        const TriSetup t = tri_setup_v(sv[i0], sv[i1], sv[i2], W, Hh);
         if (t.ok && !(cull && back_facing(t, sv, faces, perm[slot]))) {
             const int tx0 = t.bx0 / T, ty0 = t.by0 / T, tx1 = t.bx1 / T, ty1 = t.by1 / T;
             box = (uint16_t)(tx0 | (ty0 << 4) | (tx1 << 8) | (ty1 << 12));
@@ -621,48 +430,48 @@ __global__ __launch_bounds__(256) void raster_bin_kernel(const SVert* __restrict
         }
     }
     tbox[((size_t)h * nchunk + chunk) * BIN_CHUNK + lane] = box;
-    m = wave_or64(m);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m |= __shfl_xor(m, off, 64);   // the chunk's mask: OR over the wave
     if (lane == 0) cmask[(size_t)h * nchunk + chunk] = m;
 }
 
-__device__ __forceinline__ void strad_pixel_tile(const Strad& q, int f, int px, int py, unsigned long long* tile, int X0, int Y0, int T) {
-    float d, b0, b1, b2;
-    if (!strad_pixel(q, px, py, d, b0, b1, b2)) return;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)f;
-    unsigned long long* slot = &tile[(py - Y0) * T + (px - X0)];
-    if (key >= *(volatile unsigned long long*)slot) return;
-    atomicMin(slot, key);
-}
-
-__device__ __forceinline__ void tile_pixel(const TriSetup& t, int f, int px, int py, unsigned long long* tile, int X0, int Y0, int T) {
-    float b0, b1, b2, d;
-    if (t.small) {
-        int w0, w1, w2;
-        if (!tri_cover32(t, px, py, w0, w1, w2)) return;
-        d = tri_depth32(t, tri_rcp_area(t), w0, w1, w2, b0, b1, b2);   // (three IEEE quotients instead: measured 5 % slower at 1 280 triangles)
-    } else {
-        long long w0, w1, w2;
-        if (!tri_cover(t, px, py, w0, w1, w2)) return;
-        d = tri_depth(t, w0, w1, w2, b0, b1, b2);
-    }
-    if (!(d > 0.f)) return;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)f;
-    unsigned long long* slot = &tile[(py - Y0) * T + (px - X0)];
-    // stored keys only ever decrease, so a plain (possibly stale) read bounds the current value from above: a key that does
-    // not beat it cannot change the slot (LDS reads are cheap; the same test on the global buffer is a loss, see tri_pixel)
-    if (key >= *(volatile unsigned long long*)slot) return;
-    atomicMin(slot, key);
-}
-
+// what fp_depth_extents would compute from a depth image: mask count, pixel box, fp64 cloud extremes.  Every fold is a sum, a minimum or
+// a maximum: order-independent, hence bit-identical however the pixels are spread over threads, waves and tiles
 struct ExtAcc {
-    int cnt, xmin, ymin, xmax, ymax;
-    double Xmin, Xmax, Ymin, Ymax;
+    int cnt = 0, xmin = 1 << 30, ymin = 1 << 30, xmax = -1, ymax = -1;
+    double Xmin = 1e300, Xmax = -1e300, Ymin = 1e300, Ymax = -1e300;
+    // pixel (px, py) of non-zero depth d, at (X, Y) in the camera frame: every non-zero depth joins the cloud, every positive one the mask
+    __device__ __forceinline__ void add(int px, int py, double X, double Y, float d) {
+        Xmin = fmin(Xmin, X); Xmax = fmax(Xmax, X); Ymin = fmin(Ymin, Y); Ymax = fmax(Ymax, Y);
+        if (d > 0.f) { ++cnt; xmin = min(xmin, px); xmax = max(xmax, px); ymin = min(ymin, py); ymax = max(ymax, py); }
+    }
+    __device__ __forceinline__ void merge(const ExtAcc& o) {
+        cnt += o.cnt;
+        xmin = min(xmin, o.xmin); ymin = min(ymin, o.ymin); xmax = max(xmax, o.xmax); ymax = max(ymax, o.ymax);
+        Xmin = fmin(Xmin, o.Xmin); Xmax = fmax(Xmax, o.Xmax); Ymin = fmin(Ymin, o.Ymin); Ymax = fmax(Ymax, o.Ymax);
+    }
+    __device__ __forceinline__ void wave_reduce() {   // butterfly: every lane ends with the wave's fold
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            ExtAcc o;
+            o.cnt = __shfl_xor(cnt, off, 64);
+            o.xmin = __shfl_xor(xmin, off, 64); o.ymin = __shfl_xor(ymin, off, 64); o.xmax = __shfl_xor(xmax, off, 64); o.ymax = __shfl_xor(ymax, off, 64);
+            o.Xmin = __shfl_xor(Xmin, off, 64); o.Xmax = __shfl_xor(Xmax, off, 64); o.Ymin = __shfl_xor(Ymin, off, 64); o.Ymax = __shfl_xor(Ymax, off, 64);
+            merge(o);
+        }
+    }
+    // as a record: five integers (doubles in a (view, tile) record of `part`, ints in the tile kernel's LDS) and four doubles
+    template <class I> __device__ __forceinline__ void store(I* i5, double* d4) const {
+        i5[0] = (I)cnt; i5[1] = (I)xmin; i5[2] = (I)ymin; i5[3] = (I)xmax; i5[4] = (I)ymax;
+        d4[0] = Xmin; d4[1] = Xmax; d4[2] = Ymin; d4[3] = Ymax;
+    }
+    template <class I> __device__ __forceinline__ static ExtAcc load(const I* i5, const double* d4) {
+        ExtAcc e;
+        e.cnt = (int)i5[0]; e.xmin = (int)i5[1]; e.ymin = (int)i5[2]; e.xmax = (int)i5[3]; e.ymax = (int)i5[4];
+        e.Xmin = d4[0]; e.Xmax = d4[1]; e.Ymin = d4[2]; e.Ymax = d4[3];
+        return e;
+    }
 };
-__device__ __forceinline__ double shfl_xor_f64(double v, int off) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = __shfl_xor((unsigned)b, off, 64), hi = __shfl_xor((unsigned)(b >> 32), off, 64);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 // the set-up a lane holds, handed to the whole wave (lane `src` is wave-uniform: v_readlane, no memory round trip)
 __device__ __forceinline__ int rl_i(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
@@ -674,10 +483,106 @@ __device__ __forceinline__ TriSetup bcast_setup(const TriSetup& t, int src) {
     const unsigned lo = (unsigned)rl_i((int)(unsigned)(unsigned long long)t.area2, src), hi = (unsigned)rl_i((int)(unsigned)((unsigned long long)t.area2 >> 32), src);
     r.area2 = (long long)(((unsigned long long)hi << 32) | lo);
     r.bx0 = rl_i(t.bx0, src); r.by0 = rl_i(t.by0, src); r.bx1 = rl_i(t.bx1, src); r.by1 = rl_i(t.by1, src);
-    r.i0 = rl_i(t.i0, src); r.i1 = rl_i(t.i1, src); r.i2 = rl_i(t.i2, src);
     const int flags = rl_i((t.ok ? 1 : 0) | (t.swapped ? 2 : 0) | (t.strad ? 4 : 0) | (t.small ? 8 : 0), src);
     r.ok = flags & 1; r.swapped = flags & 2; r.strad = flags & 4; r.small = flags & 8;
-    return r;
+    return r;   // (word by word through memcpy was tried: +4 scalar instructions in the tile kernel, one above the parent)
+}
+
+// A lane's own (small) triangle against its <= 32 candidate pixels in the tile, in two passes: coverage of every candidate first (a few
+// integer operations each) into a bit mask, then depth + LDS minimum for the covered ones only.  The wave waits for its slowest lane in
+// both loops, so the expensive part now runs max-over-lanes(COVERED pixels) times (~1-4 for the ~1.4-pixel triangles of an 82 k mesh)
+// instead of max-over-lanes(candidates) (~12): the chunk loop was 2/3 of the kernel on that mesh.
+__device__ __forceinline__ void tile_tri_small(const TriSetup& t, int f, int x0, int y0, int x1, int y1, const TileCtx& sink) {
+    const EdgeFn e(t);
+    const int bw = x1 - x0 + 1;
+    unsigned mask = 0u;
+    int k = 0;
+    for (int py = y0; py <= y1; ++py) {
+        const int sy = pixel_centre<int>(py);
+        for (int px = x0; px <= x1; ++px, ++k) {
+            int w0, w1, w2;
+            e.weights(pixel_centre<int>(px), sy, w0, w1, w2);
+            mask |= (e.accept(w0, w1, w2) ? 1u : 0u) << k;
+        }
+    }
+    if (!mask) return;
+    const double rd = area_rcp(t);
+    const float rbw = split_rcp(bw);
+    while (mask) {
+        const int kk = __ffs((int)mask) - 1;
+        mask &= mask - 1u;
+        int ry, rx, w0, w1, w2;
+        split_rowcol(kk, bw, rbw, ry, rx);
+        const int px = x0 + rx, py = y0 + ry;
+        e.weights(pixel_centre<int>(px), pixel_centre<int>(py), w0, w1, w2);
+        const float d = depth_from_bary(t, bary_rcp(w0, rd), bary_rcp(w1, rd), bary_rcp(w2, rd));
+        if (d > 0.f) sink.put(px, py, vis_key(d, f));
+    }
+}
+
+// ---- the lab build's hooks of the tile kernel, all behind this fence (tools/raster_ablate.py, tools/lab_selfcheck.py).  raster_dbg bits 1 / 2 / 4 / 8
+// switch a stage OFF (no rasterisation / no shading / no flush / no mask scan: wrong pictures, timing only), bits 8.. = the per-lane / whole-wave threshold
+// (0 = the product's); buf = shader-clock sums of all workgroups: 0 init, 1 mask scan, 2 chunk loop (slowest wave), 3 resolve, 4 flush, 6 wave 0's chunk loop, 7 hit chunks
+#ifdef FP_LAB
+constexpr bool LAB = true;
+#else
+constexpr bool LAB = false;    // every hook below folds away: bits = 0, the product's threshold, no buffer, no clock read
+#endif
+struct Lab {
+    int bits, big_area;
+    unsigned long long *buf, tstamp;
+    __device__ __forceinline__ Lab(int arg, unsigned long long* b)
+        : bits(LAB ? arg & 255 : 0), big_area(LAB && (arg >> 8) ? min(arg >> 8, 32) : BIG_TILE_AREA),   // (the per-lane coverage mask has 32 bits)
+          buf(LAB ? b : nullptr), tstamp(LAB ? __builtin_readcyclecounter() : 0ull) {}
+    __device__ __forceinline__ bool off(int bit) const { return bits & bit; }
+    __device__ __forceinline__ void phase(int k) {
+        if (!LAB || !buf || threadIdx.x != 0) return;
+        const unsigned long long now = __builtin_readcyclecounter();
+        atomicAdd(&buf[k], now - tstamp);
+        tstamp = now;
+    }
+    __device__ __forceinline__ void chunk_stats(int n) const {
+        if (!LAB || !buf || threadIdx.x != 0) return;
+        atomicAdd(&buf[6], (unsigned long long)(__builtin_readcyclecounter() - tstamp));
+        atomicAdd(&buf[7], (unsigned long long)n);
+    }
+};
+
+// ---- the tile kernel's stages (TileCtx above)
+__device__ __forceinline__ void tile_init(const TileCtx& c, const float* __restrict__ tables, double fx, double fy, double cx, double cy,
+                                          int& nhit_s, int& total_s) {
+    const int T = c.T;
+    c.tab[threadIdx.x] = tables[threadIdx.x];
+    c.tab[threadIdx.x + 256] = tables[threadIdx.x + 256];
+    if (threadIdx.x < T) c.ax[threadIdx.x] = ((double)(c.X0 + (int)threadIdx.x) - cx) / fx;
+    else if ((int)threadIdx.x < 2 * T) c.ay[threadIdx.x - T] = ((double)(c.Y0 + (int)threadIdx.x - T) - cy) / fy;
+    for (int p = threadIdx.x; p < T * T; p += blockDim.x) c.tile[p] = KEY_NONE;
+    if (threadIdx.x == 0) { nhit_s = 0; total_s = 0; }
+    __syncthreads();
+}
+
+// which of the round's HITS_ROUND chunks (from `base`) touch this tile: coalesced mask reads, wave-compacted into the hit list
+__device__ __forceinline__ void scan_hits(const TileCtx& c, const unsigned long long* __restrict__ cm, int base, int nchunk, int& nhit_s) {
+    const int tbit = c.ty * 8 + c.tx;
+    unsigned long long mk[HITS_ROUND / 256];
+#pragma unroll
+    for (int k = 0; k < HITS_ROUND / 256; ++k) {                      // the round's mask loads in flight together
+        const int ch = base + k * 256 + (int)threadIdx.x;
+        mk[k] = ch < nchunk ? cm[ch] : 0ull;
+    }
+#pragma unroll
+    for (int k = 0; k < HITS_ROUND / 256; ++k) {
+        const int ch = base + k * 256 + (int)threadIdx.x;
+        const bool hit = (mk[k] >> tbit) & 1ull;
+        const unsigned long long bm = __ballot(hit);
+        if (bm) {                                                     // wave-uniform
+            int wbase = 0;
+            if (c.lane == 0) wbase = atomicAdd(&nhit_s, __popcll(bm));
+            wbase = __shfl(wbase, 0, 64);
+            if (hit) c.hits[wbase + __popcll(bm & ((1ull << c.lane) - 1ull))] = (unsigned short)(ch - base);
+        }
+    }
+    __syncthreads();
 }
 
 // what a lane needs of its triangle in a hit chunk: level 1 = coalesced reads in slot order (tile box, corner ids, face id),
@@ -685,329 +590,227 @@ __device__ __forceinline__ TriSetup bcast_setup(const TriSetup& t, int src) {
 // flight while chunk i is rasterised (a wave otherwise walks its ~30 chunks of an 82 k-triangle mesh one memory round trip at a time).
 struct ChunkL1 { unsigned box; int i0, i1, i2, f; };
 struct ChunkL2 { SVert a, b, c; };
-constexpr int RES_BATCH = 2;             // pixels a thread resolves together (their gathers are issued back to back)
 
-// A lane's own (small) triangle against its <= 32 candidate pixels in the tile, in two passes: coverage of every candidate first (a few
-// integer operations each) into a bit mask, then depth + LDS minimum for the covered ones only.  The wave waits for its slowest lane in
-// both loops, so the expensive part now runs max-over-lanes(COVERED pixels) times (~1-4 for the ~1.4-pixel triangles of an 82 k mesh)
-// instead of max-over-lanes(candidates) (~12): the chunk loop was 2/3 of the kernel on that mesh.
-__device__ __forceinline__ void tile_tri_small(const TriSetup& t, int f, int x0, int y0, int x1, int y1, unsigned long long* tile,
-                                               int X0, int Y0, int T) {
-    const int A0 = t.x2 - t.x1, B0 = t.y2 - t.y1, A1 = t.x0 - t.x2, B1 = t.y0 - t.y2, A2 = t.x1 - t.x0, B2 = t.y1 - t.y0;
-    const bool tl0 = topleft(A0, B0), tl1 = topleft(A1, B1), tl2 = topleft(A2, B2);
-    const int bw = x1 - x0 + 1;
-    unsigned mask = 0u;
-    int k = 0;
-    for (int py = y0; py <= y1; ++py) {
-        const int sy = py * 256 + 128;
-        for (int px = x0; px <= x1; ++px, ++k) {
-            const int sx = px * 256 + 128;
-            const int w0 = __mul24(A0, sy - t.y1) - __mul24(B0, sx - t.x1);
-            const int w1 = __mul24(A1, sy - t.y2) - __mul24(B1, sx - t.x2);
-            const int w2 = __mul24(A2, sy - t.y0) - __mul24(B2, sx - t.x0);
-            const bool in = (w0 | w1 | w2) >= 0 && (w0 != 0 || tl0) && (w1 != 0 || tl1) && (w2 != 0 || tl2);
-            mask |= (in ? 1u : 0u) << k;
+// Every wave takes hit chunks (the first n of the hit list) on its own, one triangle per lane; above big_area candidate pixels: the whole wave
+__device__ __forceinline__ void chunk_loop(const TileCtx& c, int n, int base, const uint16_t* __restrict__ tb, const int32_t* __restrict__ fsort,
+                                           const int32_t* __restrict__ perm, int F, int big_area) {
+    const int lane = c.lane, tx = c.tx, ty = c.ty, X0 = c.X0, Y0 = c.Y0, X1 = c.X1, Y1 = c.Y1, W = c.W, Hh = c.Hh;
+    const SVert* sv = c.sv;
+    auto level1 = [&](int i, ChunkL1& l) {
+        l.box = TBOX_NONE; l.i0 = l.i1 = l.i2 = 0; l.f = 0;
+        if (i < n) {
+            const int slot = (base + (int)c.hits[i]) * BIN_CHUNK + lane;
+            l.box = tb[slot];                                        // (TBOX_NONE for slots >= F)
+            if (slot < F) { l.i0 = fsort[3 * slot]; l.i1 = fsort[3 * slot + 1]; l.i2 = fsort[3 * slot + 2]; l.f = perm[slot]; }
         }
-    }
-    if (!mask) return;
-    const double rd = tri_rcp_area(t);
-    const float rbw = 1.0f / (float)bw;
-    while (mask) {
-        const int kk = __ffs((int)mask) - 1;
-        mask &= mask - 1u;
-        const int ry = (int)(((float)kk + 0.5f) * rbw), rx = kk - ry * bw;      // kk / bw for kk < 32, bw <= 32
-        const int px = x0 + rx, py = y0 + ry;
-        const int sx = px * 256 + 128, sy = py * 256 + 128;
-        const int w0 = __mul24(A0, sy - t.y1) - __mul24(B0, sx - t.x1);
-        const int w1 = __mul24(A1, sy - t.y2) - __mul24(B1, sx - t.x2);
-        const int w2 = __mul24(A2, sy - t.y0) - __mul24(B2, sx - t.x0);
-        float b0, b1, b2;
-        const float d = tri_depth32(t, rd, w0, w1, w2, b0, b1, b2);
-        if (!(d > 0.f)) continue;
-        const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)f;
-        unsigned long long* slot = &tile[(py - Y0) * T + (px - X0)];
-        if (key < *(volatile unsigned long long*)slot) atomicMin(slot, key);
+    };
+    auto overlaps = [&](unsigned box) {
+        const int bx0 = box & 15, by0 = (box >> 4) & 15, bx1 = (box >> 8) & 15, by1 = (box >> 12) & 15;
+        return bx0 <= tx && tx <= bx1 && by0 <= ty && ty <= by1;
+    };
+    auto level2 = [&](const ChunkL1& l, ChunkL2& g) {   // (lanes whose triangle misses the tile read vertex 0: one cached line, no branch, no zero fill)
+        const bool o = overlaps(l.box);
+        g.a = sv[o ? l.i0 : 0]; g.b = sv[o ? l.i1 : 0]; g.c = sv[o ? l.i2 : 0];
+    };
+    ChunkL1 c0, c1, c2;
+    ChunkL2 g0, g1;
+    level1(c.wave, c0);
+    level1(c.wave + 4, c1);
+    level2(c0, g0);
+    for (int i = c.wave; i < n; i += 4) {
+        level1(i + 8, c2);
+        level2(c1, g1);
+        // set-up on every lane (a wave executes it once whatever the number of live lanes; a branch only added register traffic)
+        const int f = c0.f;
+        const TriSetup t = tri_setup_v(g0.a, g0.b, g0.c, W, Hh);
+        const int x0 = max(t.bx0, X0), y0 = max(t.by0, Y0), x1 = min(t.bx1, X1), y1 = min(t.by1, Y1);
+        const bool mine = overlaps(c0.box) && t.ok && x0 <= x1 && y0 <= y1;
+        // the wave loop: many candidate pixels, edge functions beyond 32 bits, near-plane straddlers
+        const bool big = mine && ((x1 - x0 + 1) * (y1 - y0 + 1) > big_area || !t.small || t.strad);
+        if (mine && !big) tile_tri_small(t, f, x0, y0, x1, y1, c);
+        // triangles with many candidate pixels in this tile, and near-plane straddlers: the whole wave strides over them, one triangle
+        // at a time, the owner lane's set-up broadcast by v_readlane.  (Round 6 also measured the candidates of a chunk FLATTENED over
+        // the lanes — counts prefix-summed, owner found by binary search, set-up fetched by ds_bpermute: 14 permutes per item cost what
+        // the idle lanes did; 2.32 / 3.03 / 6.29 ms against 1.70 / 3.13 / 5.26 at 1 280 / 81 920 / 327 680 triangles.  Not shipped.)
+        unsigned long long bm = __ballot(big);
+        while (bm) {
+            const int src = __ffsll((long long)bm) - 1;
+            bm &= bm - 1;
+            const int fb = rl_i(f, src);
+            const TriSetup tbg = bcast_setup(t, src);          // (was a second set-up from memory: two dependent gathers per triangle)
+            const int ax0 = max(tbg.bx0, X0), ay0 = max(tbg.by0, Y0), ax1 = min(tbg.bx1, X1), ay1 = min(tbg.by1, Y1);
+            wave_rasterize(tbg, sv, c.faces, fb, ax0, ay0, ax1 - ax0 + 1, (ax1 - ax0 + 1) * (ay1 - ay0 + 1), lane, c);
+        }
+        c0 = c1; c1 = c2; g0 = g1;
     }
 }
 
-__global__ __launch_bounds__(256) void raster_tile_kernel(const SVert* __restrict__ sv_all, const int32_t* __restrict__ faces,
-                                                          const int32_t* __restrict__ perm, const int32_t* __restrict__ fsort, ShadeArgs sh,
-                                                          const float* __restrict__ tables, int V, int F, int W, int Hh, int T,
-                                                          int ntx, int Hn, const uint16_t* __restrict__ tbox,
-                                                          const unsigned long long* __restrict__ cmask, int nchunk,
-                                                          uint8_t* __restrict__ rgb, float* __restrict__ depth,
-                                                          double* __restrict__ part, double fx, double fy, double cx, double cy,
-                                                          int dbg_arg, unsigned long long* dbg_buf) {
-#ifdef FP_LAB   // lab build: ablation bits for tools/raster_ablate.py (1 = no rasterisation, 2 = no shading, 4 = no flush, 8 = no mask scan),
-    // bits 8.. = the per-lane / whole-wave threshold (0 = the product's), dbg_buf = per-phase shader-clock sums of all workgroups
-    const int dbg = dbg_arg & 255;
-    const int big_area = (dbg_arg >> 8) ? min(dbg_arg >> 8, 32) : BIG_TILE_AREA;   // (the per-lane coverage mask has 32 bits)
-    unsigned long long tstamp = __builtin_readcyclecounter();
-#define FP_RASTER_PHASE(k)                                                                                   \
-    do {                                                                                                     \
-        if (dbg_buf && threadIdx.x == 0) {                                                                   \
-            const unsigned long long now__ = __builtin_readcyclecounter();                                   \
-            atomicAdd(&dbg_buf[k], now__ - tstamp);                                                          \
-            tstamp = now__;                                                                                  \
-        }                                                                                                    \
-    } while (0)
-#else
-    constexpr int dbg = 0;
-    constexpr int big_area = BIG_TILE_AREA;
-    (void)dbg_arg; (void)dbg_buf;
-#define FP_RASTER_PHASE(k) do {} while (0)
-#endif
-    extern __shared__ unsigned long long tile[];   // [T*T] visibility keys | DEC/THR tables (512 floats) | hit list | column / row factors
-    float* tab = (float*)(tile + T * T);
-    unsigned short* hits = (unsigned short*)(tab + 512);
-    double* ax = (double*)(hits + HITS_ROUND);
-    double* ay = ax + T;
-    __shared__ int nhit_s, total_s;
-    __shared__ double red_d[4][4];
-    __shared__ int red_i[4][5];
-    int tidx, h;
-    view_major_ids(gridDim.x, Hn, tidx, h);
-    const int ty = tidx / ntx, tx = tidx - ty * ntx;
-    const int X0 = tx * T, Y0 = ty * T;
-    const int X1 = min(W - 1, X0 + T - 1), Y1 = min(Hh - 1, Y0 + T - 1);
-    const SVert* sv = sv_all + (size_t)h * V;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    tab[threadIdx.x] = tables[threadIdx.x];
-    tab[threadIdx.x + 256] = tables[threadIdx.x + 256];
-    if (threadIdx.x < T) ax[threadIdx.x] = ((double)(X0 + (int)threadIdx.x) - cx) / fx;
-    else if ((int)threadIdx.x < 2 * T) ay[threadIdx.x - T] = ((double)(Y0 + (int)threadIdx.x - T) - cy) / fy;
-    for (int p = threadIdx.x; p < T * T; p += blockDim.x) tile[p] = ~0ull;
-    if (threadIdx.x == 0) { nhit_s = 0; total_s = 0; }
+constexpr int RES_BATCH = 2;             // pixels a thread resolves together (their gathers are issued back to back)
+
+// resolve: same arithmetic as raster_resolve_kernel; the result replaces the pixel's key in its own LDS slot, and joins the thread's extents `e`.
+// RES_BATCH pixels per thread at a time: keys -> corner ids -> vertices + attributes, each level's loads issued for the whole batch before the first is used
+// (a pixel at a time, the three dependent gathers bound the whole kernel: 2 ms per 576 views).  A tile no chunk touched is background.  shade: false in the lab only
+__device__ __forceinline__ void resolve_tile(const TileCtx& c, bool touched, const ShadeArgs& sh, bool shade, ExtAcc& e) {
+    const int T = c.T, tw = c.tw(), th = c.th(), W = c.W, Hh = c.Hh;
+    unsigned long long* tile = c.tile;
+    if (!touched) {
+        for (int p = threadIdx.x; p < T * T; p += blockDim.x) tile[p] = 0ull;
+        __syncthreads();
+        return;
+    }
+    for (int pb = threadIdx.x; pb < tw * th; pb += blockDim.x * RES_BATCH) {
+        unsigned long long key[RES_BATCH];
+        int lxs[RES_BATCH], lys[RES_BATCH], ids[RES_BATCH][3];
+        SVert va[RES_BATCH], vb[RES_BATCH], vc[RES_BATCH];
+        TriAttr at[RES_BATCH];
+#pragma unroll
+        for (int k = 0; k < RES_BATCH; ++k) {
+            const int p = pb + k * (int)blockDim.x;
+            key[k] = KEY_NONE; lxs[k] = lys[k] = 0;
+            if (p < tw * th) { lys[k] = p / tw; lxs[k] = p - lys[k] * tw; key[k] = tile[lys[k] * T + lxs[k]]; }
+        }
+#pragma unroll
+        for (int k = 0; k < RES_BATCH; ++k) {
+            ids[k][0] = ids[k][1] = ids[k][2] = 0;
+            if (key[k] != KEY_NONE) {
+                const int f = key_face(key[k]);
+                ids[k][0] = c.faces[3 * f]; ids[k][1] = c.faces[3 * f + 1]; ids[k][2] = c.faces[3 * f + 2];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < RES_BATCH; ++k) {
+            if (key[k] != KEY_NONE) {
+                va[k] = c.sv[ids[k][0]]; vb[k] = c.sv[ids[k][1]]; vc[k] = c.sv[ids[k][2]];
+                at[k] = load_attr(sh, key_face(key[k]), ids[k][0], ids[k][1], ids[k][2]);
+            } else {
+                va[k] = vb[k] = vc[k] = SVert{0, 0, 0.f, 0.f};
+                at[k] = TriAttr{};
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < RES_BATCH; ++k) {
+            const int p = pb + k * (int)blockDim.x;
+            if (p >= tw * th) continue;
+            const int lx = lxs[k], ly = lys[k], px = c.X0 + lx, py = c.Y0 + ly;
+            float d = 0.f;
+            uint8_t out[3] = {0, 0, 0};
+            if (key[k] != KEY_NONE && shade) {
+                const TriSetup t = tri_setup_v(va[k], vb[k], vc[k], W, Hh);
+                resolve_pixel_v<TileCtx::NARROW>(c.sv, c.faces, sh, c.tab, key[k], t, at[k], px, py, d, out);
+            }
+            tile[ly * T + lx] = vis_key(d, 0) | (unsigned)out[0] | ((unsigned)out[1] << 8) | ((unsigned)out[2] << 16);
+            if (d != 0.f) e.add(px, py, c.ax[lx] * (double)d, c.ay[ly] * (double)d, d);
+        }
+    }
     __syncthreads();
-    FP_RASTER_PHASE(0);                                // init
-    const int tbit = ty * 8 + tx;
-    const unsigned long long* cm = cmask + (size_t)h * nchunk;
-    const uint16_t* tb = tbox + (size_t)h * nchunk * BIN_CHUNK;
-    for (int base = 0; base < ((dbg & 8) ? 0 : nchunk); base += HITS_ROUND) {
-        // ---- which of the next 2048 chunks touch this tile: coalesced mask reads, wave-compacted into the hit list
-        unsigned long long mk[HITS_ROUND / 256];
+}
+
+// ---- flush: depth rows as floats; rgb rows as whole dwords (byte stores only for a row's unaligned ends)
+__device__ __forceinline__ void flush_depth(const TileCtx& c, float* __restrict__ depth) {
+    const int tw = c.tw(), th = c.th(), W = c.W, Hh = c.Hh;
+    for (int p = threadIdx.x; p < tw * th; p += blockDim.x) {
+        const int ly = p / tw, lx = p - ly * tw;
+        depth[((size_t)c.h * Hh + c.Y0 + ly) * W + c.X0 + lx] = key_depth(c.tile[ly * c.T + lx]);
+    }
+}
+// rows start on a dword (W * 3 and X0 * 3 are multiples of 4) and hold whole groups of four pixels = three dwords: the packed results'
+// low words are spliced with shifts, one 12-byte store per lane, adjacent lanes adjacent
+__device__ __forceinline__ void flush_rgb_dword(const TileCtx& c, uint8_t* __restrict__ rgb) {
+    const int nq = c.tw() >> 2, th = c.th(), W = c.W, Hh = c.Hh;
+    for (int q = threadIdx.x; q < th * nq; q += blockDim.x) {
+        const int ly = q / nq, qx = q - ly * nq;
+        const unsigned long long* src = &c.tile[ly * c.T + 4 * qx];
+        const unsigned p0 = (unsigned)src[0], p1 = (unsigned)src[1], p2 = (unsigned)src[2], p3 = (unsigned)src[3];
+        uint3 o;
+        o.x = (p0 & 0xffffffu) | (p1 << 24);
+        o.y = ((p1 >> 8) & 0xffffu) | (p2 << 16);
+        o.z = ((p2 >> 16) & 0xffu) | (p3 << 8);
+        *(uint3*)(rgb + (((size_t)c.h * Hh + c.Y0 + ly) * W + c.X0 + 4 * qx) * 3) = o;
+    }
+}
+// any width and alignment: one aligned dword per thread, stored whole when all four bytes belong to the tile row, else byte by byte
+__device__ __forceinline__ void flush_rgb_bytes(const TileCtx& c, uint8_t* __restrict__ rgb) {
+    const int tw = c.tw(), th = c.th(), W = c.W, Hh = c.Hh;
+    const int ndw = (tw * 3 + 3) / 4 + 1;                          // dwords that can hold a row's bytes at any alignment
+    for (int q = threadIdx.x; q < th * ndw; q += blockDim.x) {
+        const int ly = q / ndw, j = q - ly * ndw;
+        const size_t start = (((size_t)c.h * Hh + c.Y0 + ly) * W + c.X0) * 3;   // first byte of the tile row in the rgb buffer
+        const size_t a = (start & ~(size_t)3) + (size_t)j * 4;            // this thread's aligned dword
+        const long long o0 = (long long)a - (long long)start;              // row-relative offset of its first byte
+        if (o0 >= (long long)tw * 3) continue;
+        unsigned v = 0;
+        bool in[4];
 #pragma unroll
-        for (int k = 0; k < HITS_ROUND / 256; ++k) {                      // the round's four mask loads in flight together
-            const int c = base + k * 256 + (int)threadIdx.x;
-            mk[k] = c < nchunk ? cm[c] : 0ull;
+        for (int k = 0; k < 4; ++k) {
+            const long long o = o0 + k;
+            in[k] = o >= 0 && o < (long long)tw * 3;
+            if (in[k]) {
+                const int pix = (int)o / 3, ch = (int)o - pix * 3;
+                v |= (unsigned)((c.tile[ly * c.T + pix] >> (8 * ch)) & 255ull) << (8 * k);
+            }
         }
+        if (in[0] && in[3]) *(uint32_t*)(rgb + a) = v;
+        else {
 #pragma unroll
-        for (int k = 0; k < HITS_ROUND / 256; ++k) {
-            const int c = base + k * 256 + (int)threadIdx.x;
-            const bool hit = (mk[k] >> tbit) & 1ull;
-            const unsigned long long bm = __ballot(hit);
-            if (bm) {                                                     // wave-uniform
-                int wbase = 0;
-                if (lane == 0) wbase = atomicAdd(&nhit_s, __popcll(bm));
-                wbase = __shfl(wbase, 0, 64);
-                if (hit) hits[wbase + __popcll(bm & ((1ull << lane) - 1ull))] = (unsigned short)(c - base);
-            }
+            for (int k = 0; k < 4; ++k) if (in[k]) rgb[a + k] = (uint8_t)(v >> (8 * k));
         }
+    }
+}
+
+// the tile's extents record: the threads' accumulators folded over each wave, then over the four waves through LDS
+__device__ __forceinline__ void write_extents_record(const TileCtx& c, ExtAcc e, int (&red_i)[4][5], double (&red_d)[4][4], double* __restrict__ rec) {
+    e.wave_reduce();
+    if (c.lane == 0) e.store(red_i[c.wave], red_d[c.wave]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ExtAcc all = ExtAcc::load(red_i[0], red_d[0]);
+        for (int w = 1; w < 4; ++w) all.merge(ExtAcc::load(red_i[w], red_d[w]));
+        all.store(rec, rec + 5);
+    }
+}
+
+__global__ __launch_bounds__(256) void raster_tile_kernel(
+    const SVert* __restrict__ sv_all, const int32_t* __restrict__ faces, const int32_t* __restrict__ perm, const int32_t* __restrict__ fsort, ShadeArgs sh,
+    const float* __restrict__ tables, int V, int F, int W, int Hh, int T, int ntx, int Hn, const uint16_t* __restrict__ tbox,
+    const unsigned long long* __restrict__ cmask, int nchunk, uint8_t* __restrict__ rgb, float* __restrict__ depth, double* __restrict__ part, double fx,
+    double fy, double cx, double cy, int dbg_arg, unsigned long long* dbg_buf) {
+    Lab lab(dbg_arg, dbg_buf);
+    extern __shared__ unsigned long long tile[];   // [T*T] visibility keys | DEC/THR tables (512 floats) | hit list | column / row factors
+    __shared__ int nhit_s, total_s;
+    __shared__ double red_d[4][4];                 // the four waves' extents, folded by write_extents_record
+    __shared__ int red_i[4][5];
+    TileCtx c;
+    int tidx;
+    view_major(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, Hn, tidx, c.h);   // all tiles of a view on one XCD (raster_plan.h)
+    c.ty = tidx / ntx; c.tx = tidx - c.ty * ntx; c.T = T; c.W = W; c.Hh = Hh;
+    c.X0 = c.tx * T; c.Y0 = c.ty * T; c.X1 = min(W - 1, c.X0 + T - 1); c.Y1 = min(Hh - 1, c.Y0 + T - 1);
+    c.tile = tile; c.tab = (float*)(tile + T * T); c.hits = (unsigned short*)(c.tab + 512);
+    c.ax = (double*)(c.hits + HITS_ROUND); c.ay = c.ax + T;
+    c.sv = sv_all + (size_t)c.h * V; c.faces = faces; c.lane = threadIdx.x & 63; c.wave = threadIdx.x >> 6;
+    tile_init(c, tables, fx, fy, cx, cy, nhit_s, total_s);
+    lab.phase(0);
+    const unsigned long long* cm = cmask + (size_t)c.h * nchunk;
+    const uint16_t* tb = tbox + (size_t)c.h * nchunk * BIN_CHUNK;
+    for (int base = 0; base < (lab.off(8) ? 0 : nchunk); base += HITS_ROUND) {
+        scan_hits(c, cm, base, nchunk, nhit_s);
+        lab.phase(1);
+        const int n = lab.off(1) ? 0 : nhit_s;
+        chunk_loop(c, n, base, tb, fsort, perm, F, lab.big_area);
+        lab.chunk_stats(n);
         __syncthreads();
-        FP_RASTER_PHASE(1);                            // mask scan
-        const int n = (dbg & 1) ? 0 : nhit_s;
-        // ---- every wave takes hit chunks on its own: one triangle per lane, software-pipelined over the wave's chunks
-        auto level1 = [&](int i, ChunkL1& c) {
-            c.box = TBOX_NONE; c.i0 = c.i1 = c.i2 = 0; c.f = 0;
-            if (i < n) {
-                const int slot = (base + (int)hits[i]) * BIN_CHUNK + lane;
-                c.box = tb[slot];                                        // (TBOX_NONE for slots >= F)
-                if (slot < F) { c.i0 = fsort[3 * slot]; c.i1 = fsort[3 * slot + 1]; c.i2 = fsort[3 * slot + 2]; c.f = perm[slot]; }
-            }
-        };
-        auto overlaps = [&](unsigned box) {
-            const int bx0 = box & 15, by0 = (box >> 4) & 15, bx1 = (box >> 8) & 15, by1 = (box >> 12) & 15;
-            return bx0 <= tx && tx <= bx1 && by0 <= ty && ty <= by1;
-        };
-        auto level2 = [&](const ChunkL1& c, ChunkL2& g) {   // (lanes whose triangle misses the tile read vertex 0: one cached line, no branch, no zero fill)
-            const bool o = overlaps(c.box);
-            g.a = sv[o ? c.i0 : 0]; g.b = sv[o ? c.i1 : 0]; g.c = sv[o ? c.i2 : 0];
-        };
-        ChunkL1 c0, c1, c2;
-        ChunkL2 g0, g1;
-        level1(wave, c0);
-        level1(wave + 4, c1);
-        level2(c0, g0);
-        for (int i = wave; i < n; i += 4) {
-            level1(i + 8, c2);
-            level2(c1, g1);
-            // set-up on every lane (a wave executes it once whatever the number of live lanes; a branch only added register traffic)
-            const int f = c0.f;
-            const TriSetup t = tri_setup_v(g0.a, g0.b, g0.c, c0.i0, c0.i1, c0.i2, W, Hh);
-            const int x0 = max(t.bx0, X0), y0 = max(t.by0, Y0), x1 = min(t.bx1, X1), y1 = min(t.by1, Y1);
-            const bool mine = overlaps(c0.box) && t.ok && x0 <= x1 && y0 <= y1;
-            // the wave loop: many candidate pixels, edge functions beyond 32 bits, near-plane straddlers
-            const bool big = mine && ((x1 - x0 + 1) * (y1 - y0 + 1) > big_area || !t.small || t.strad);
-            if (mine && !big) tile_tri_small(t, f, x0, y0, x1, y1, tile, X0, Y0, T);
-            // triangles with many candidate pixels in this tile, and near-plane straddlers: the whole wave strides over them, one triangle
-            // at a time, the owner lane's set-up broadcast by v_readlane.  (Round 6 also measured the candidates of a chunk FLATTENED over
-            // the lanes — counts prefix-summed, owner found by binary search, set-up fetched by ds_bpermute: 14 permutes per item cost what
-            // the idle lanes did; 2.32 / 3.03 / 6.29 ms against 1.70 / 3.13 / 5.26 at 1 280 / 81 920 / 327 680 triangles.  Not shipped.)
-            unsigned long long bm = __ballot(big);
-            while (bm) {
-                const int src = __ffsll((long long)bm) - 1;
-                bm &= bm - 1;
-                const int fb = rl_i(f, src);
-                const TriSetup tbg = bcast_setup(t, src);          // (was a second set-up from memory: two dependent gathers per triangle)
-                const int ax0 = max(tbg.bx0, X0), ay0 = max(tbg.by0, Y0), ax1 = min(tbg.bx1, X1), ay1 = min(tbg.by1, Y1);
-                const int bw = ax1 - ax0 + 1, np = bw * (ay1 - ay0 + 1);
-                if (tbg.strad) {
-                    const Strad sq = strad_setup(sv, faces, fb);
-                    for (int j = lane; j < np; j += 64) strad_pixel_tile(sq, fb, ax0 + j % bw, ay0 + j / bw, tile, X0, Y0, T);
-                    continue;
-                }
-                for (int j = lane; j < np; j += 64) tile_pixel(tbg, fb, ax0 + j % bw, ay0 + j / bw, tile, X0, Y0, T);
-            }
-            c0 = c1; c1 = c2; g0 = g1;
-        }
-#ifdef FP_LAB
-        if (dbg_buf && lane == 0 && wave == 0) atomicAdd(&dbg_buf[6], (unsigned long long)(__builtin_readcyclecounter() - tstamp));   // wave 0's own chunk loop
-        if (dbg_buf && threadIdx.x == 0) atomicAdd(&dbg_buf[7], (unsigned long long)n);
-#endif
-        __syncthreads();
-        FP_RASTER_PHASE(2);                            // chunk loop (until the slowest wave is done)
+        lab.phase(2);
         if (threadIdx.x == 0) { total_s += n; nhit_s = 0; }
         __syncthreads();
     }
-    const int tw = X1 - X0 + 1, th = Y1 - Y0 + 1;
-    const bool touched = total_s > 0;                  // workgroup-uniform
     ExtAcc e;
-    e.cnt = 0; e.xmin = 1 << 30; e.ymin = 1 << 30; e.xmax = -1; e.ymax = -1;
-    e.Xmin = 1e300; e.Xmax = -1e300; e.Ymin = 1e300; e.Ymax = -1e300;
-    if (touched) {
-        // ---- resolve: same arithmetic as raster_resolve_kernel; the result replaces the pixel's key in its own LDS slot.
-        // RES_BATCH pixels per thread at a time: keys -> corner ids -> vertices + attributes, each level's loads issued for the whole
-        // batch before the first is used (a pixel at a time, the three dependent gathers bound the whole kernel: 2 ms per 576 views
-        // whatever the triangle count)
-        for (int pb = threadIdx.x; pb < tw * th; pb += blockDim.x * RES_BATCH) {
-            unsigned long long key[RES_BATCH];
-            int lxs[RES_BATCH], lys[RES_BATCH], ids[RES_BATCH][3];
-            SVert va[RES_BATCH], vb[RES_BATCH], vc[RES_BATCH];
-            TriAttr at[RES_BATCH];
-#pragma unroll
-            for (int k = 0; k < RES_BATCH; ++k) {
-                const int p = pb + k * (int)blockDim.x;
-                key[k] = ~0ull; lxs[k] = lys[k] = 0;
-                if (p < tw * th) { lys[k] = p / tw; lxs[k] = p - lys[k] * tw; key[k] = tile[lys[k] * T + lxs[k]]; }
-            }
-#pragma unroll
-            for (int k = 0; k < RES_BATCH; ++k) {
-                ids[k][0] = ids[k][1] = ids[k][2] = 0;
-                if (key[k] != ~0ull) {
-                    const int f = (int)(unsigned)(key[k] & 0xffffffffu);
-                    ids[k][0] = faces[3 * f]; ids[k][1] = faces[3 * f + 1]; ids[k][2] = faces[3 * f + 2];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < RES_BATCH; ++k) {
-                if (key[k] != ~0ull) {
-                    va[k] = sv[ids[k][0]]; vb[k] = sv[ids[k][1]]; vc[k] = sv[ids[k][2]];
-                    at[k] = load_attr(sh, (int)(unsigned)(key[k] & 0xffffffffu), ids[k][0], ids[k][1], ids[k][2]);
-                } else {
-                    va[k] = vb[k] = vc[k] = SVert{0, 0, 0.f, 0.f};
-                    at[k] = TriAttr{};
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < RES_BATCH; ++k) {
-                const int p = pb + k * (int)blockDim.x;
-                if (p >= tw * th) continue;
-                const int lx = lxs[k], ly = lys[k], px = X0 + lx, py = Y0 + ly;
-                float d = 0.f;
-                uint8_t out[3] = {0, 0, 0};
-                if (key[k] != ~0ull && !(dbg & 2)) {
-                    const TriSetup t = tri_setup_v(va[k], vb[k], vc[k], ids[k][0], ids[k][1], ids[k][2], W, Hh);
-                    resolve_pixel_v(sv, faces, sh, tab, key[k], t, at[k], px, py, d, out);
-                }
-                tile[ly * T + lx] = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)out[0] | ((unsigned)out[1] << 8) | ((unsigned)out[2] << 16);
-                if (d != 0.f) {   // fp_depth_extents: every non-zero depth joins the cloud, every positive one the mask
-                    const double X = ax[lx] * (double)d, Y = ay[ly] * (double)d;
-                    e.Xmin = fmin(e.Xmin, X); e.Xmax = fmax(e.Xmax, X); e.Ymin = fmin(e.Ymin, Y); e.Ymax = fmax(e.Ymax, Y);
-                    if (d > 0.f) { ++e.cnt; e.xmin = min(e.xmin, px); e.xmax = max(e.xmax, px); e.ymin = min(e.ymin, py); e.ymax = max(e.ymax, py); }
-                }
-            }
-        }
-    } else {
-        for (int p = threadIdx.x; p < T * T; p += blockDim.x) tile[p] = 0ull;
-    }
-    __syncthreads();
-    FP_RASTER_PHASE(3);                                // resolve
-    // ---- flush: depth rows as floats; rgb rows as whole dwords (byte stores only for a row's unaligned ends)
-    if (dbg & 4) return;
-    if (depth) {
-        for (int p = threadIdx.x; p < tw * th; p += blockDim.x) {
-            const int ly = p / tw, lx = p - ly * tw;
-            depth[((size_t)h * Hh + Y0 + ly) * W + X0 + lx] = __uint_as_float((unsigned)(tile[ly * T + lx] >> 32));
-        }
-    }
-    if (((W * 3) & 3) == 0 && (tw & 3) == 0 && (T & 3) == 0) {
-        // rows start on a dword (W * 3 and X0 * 3 are multiples of 4) and hold whole groups of four pixels = three dwords: the
-        // packed results' low words are spliced with shifts, one 12-byte store per lane, adjacent lanes adjacent
-        const int nq = tw >> 2;
-        for (int q = threadIdx.x; q < th * nq; q += blockDim.x) {
-            const int ly = q / nq, qx = q - ly * nq;
-            const unsigned long long* src = &tile[ly * T + 4 * qx];
-            const unsigned p0 = (unsigned)src[0], p1 = (unsigned)src[1], p2 = (unsigned)src[2], p3 = (unsigned)src[3];
-            uint3 o;
-            o.x = (p0 & 0xffffffu) | (p1 << 24);
-            o.y = ((p1 >> 8) & 0xffffu) | (p2 << 16);
-            o.z = ((p2 >> 16) & 0xffu) | (p3 << 8);
-            *(uint3*)(rgb + (((size_t)h * Hh + Y0 + ly) * W + X0 + 4 * qx) * 3) = o;
-        }
-    } else {
-        const int ndw = (tw * 3 + 3) / 4 + 1;                          // dwords that can hold a row's bytes at any alignment
-        for (int q = threadIdx.x; q < th * ndw; q += blockDim.x) {
-            const int ly = q / ndw, j = q - ly * ndw;
-            const size_t start = (((size_t)h * Hh + Y0 + ly) * W + X0) * 3;   // first byte of the tile row in the rgb buffer
-            const size_t a = (start & ~(size_t)3) + (size_t)j * 4;            // this thread's aligned dword
-            const long long o0 = (long long)a - (long long)start;              // row-relative offset of its first byte
-            if (o0 >= (long long)tw * 3) continue;
-            unsigned v = 0;
-            bool in[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const long long o = o0 + k;
-                in[k] = o >= 0 && o < (long long)tw * 3;
-                if (in[k]) {
-                    const int pix = (int)o / 3, ch = (int)o - pix * 3;
-                    v |= (unsigned)((tile[ly * T + pix] >> (8 * ch)) & 255ull) << (8 * k);
-                }
-            }
-            if (in[0] && in[3]) *(uint32_t*)(rgb + a) = v;
-            else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (in[k]) rgb[a + k] = (uint8_t)(v >> (8 * k));
-            }
-        }
-    }
-    FP_RASTER_PHASE(4);                                // flush
-    if (!part) return;
-    // ---- the tile's extents record
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        e.cnt += __shfl_xor(e.cnt, off, 64);
-        e.xmin = min(e.xmin, __shfl_xor(e.xmin, off, 64)); e.ymin = min(e.ymin, __shfl_xor(e.ymin, off, 64));
-        e.xmax = max(e.xmax, __shfl_xor(e.xmax, off, 64)); e.ymax = max(e.ymax, __shfl_xor(e.ymax, off, 64));
-        e.Xmin = fmin(e.Xmin, shfl_xor_f64(e.Xmin, off)); e.Xmax = fmax(e.Xmax, shfl_xor_f64(e.Xmax, off));
-        e.Ymin = fmin(e.Ymin, shfl_xor_f64(e.Ymin, off)); e.Ymax = fmax(e.Ymax, shfl_xor_f64(e.Ymax, off));
-    }
-    if (lane == 0) {
-        red_i[wave][0] = e.cnt; red_i[wave][1] = e.xmin; red_i[wave][2] = e.ymin; red_i[wave][3] = e.xmax; red_i[wave][4] = e.ymax;
-        red_d[wave][0] = e.Xmin; red_d[wave][1] = e.Xmax; red_d[wave][2] = e.Ymin; red_d[wave][3] = e.Ymax;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) {
-            red_i[0][0] += red_i[w][0];
-            red_i[0][1] = min(red_i[0][1], red_i[w][1]); red_i[0][2] = min(red_i[0][2], red_i[w][2]);
-            red_i[0][3] = max(red_i[0][3], red_i[w][3]); red_i[0][4] = max(red_i[0][4], red_i[w][4]);
-            red_d[0][0] = fmin(red_d[0][0], red_d[w][0]); red_d[0][1] = fmax(red_d[0][1], red_d[w][1]);
-            red_d[0][2] = fmin(red_d[0][2], red_d[w][2]); red_d[0][3] = fmax(red_d[0][3], red_d[w][3]);
-        }
-        double* o = part + ((size_t)h * gridDim.x + tidx) * PART_N;
-        for (int k = 0; k < 5; ++k) o[k] = (double)red_i[0][k];
-        for (int k = 0; k < 4; ++k) o[5 + k] = red_d[0][k];
-    }
+    resolve_tile(c, total_s > 0, sh, !lab.off(2), e);
+    lab.phase(3);
+    if (lab.off(4)) return;
+    if (depth) flush_depth(c, depth);
+    if (((W * 3) & 3) == 0 && (c.tw() & 3) == 0 && (T & 3) == 0) flush_rgb_dword(c, rgb);
+    else flush_rgb_bytes(c, rgb);
+    lab.phase(4);
+    if (part) write_extents_record(c, e, red_i, red_d, part + ((size_t)c.h * gridDim.x + tidx) * PART_N);
 }
 
 // folds the per-tile records of a view into fp_depth_extents' row (and the int32 box CropResizePad takes): same rule for views with
@@ -1015,23 +818,14 @@ __global__ __launch_bounds__(256) void raster_tile_kernel(const SVert* __restric
 __global__ __launch_bounds__(64) void raster_extents_kernel(const double* __restrict__ part, int Hn, int ntile, int W, int Hh,
                                                             double* __restrict__ ext, int32_t* __restrict__ boxes) {
     const int v = blockIdx.x, lane = threadIdx.x;        // one wave per view, one tile record per lane (<= 64 tiles), butterfly reduction
-    int c = 0, bx0 = 1 << 30, by0 = 1 << 30, bx1 = -1, by1 = -1;
-    double Xmin = 1e300, Xmax = -1e300, Ymin = 1e300, Ymax = -1e300;
+    ExtAcc e;
     for (int t = lane; t < ntile; t += 64) {
         const double* p = part + ((size_t)v * ntile + t) * PART_N;
-        c += (int)p[0];
-        bx0 = min(bx0, (int)p[1]); by0 = min(by0, (int)p[2]); bx1 = max(bx1, (int)p[3]); by1 = max(by1, (int)p[4]);
-        Xmin = fmin(Xmin, p[5]); Xmax = fmax(Xmax, p[6]); Ymin = fmin(Ymin, p[7]); Ymax = fmax(Ymax, p[8]);
+        e.merge(ExtAcc::load(p, p + 5));
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        c += __shfl_xor(c, off, 64);
-        bx0 = min(bx0, __shfl_xor(bx0, off, 64)); by0 = min(by0, __shfl_xor(by0, off, 64));
-        bx1 = max(bx1, __shfl_xor(bx1, off, 64)); by1 = max(by1, __shfl_xor(by1, off, 64));
-        Xmin = fmin(Xmin, shfl_xor_f64(Xmin, off)); Xmax = fmax(Xmax, shfl_xor_f64(Xmax, off));
-        Ymin = fmin(Ymin, shfl_xor_f64(Ymin, off)); Ymax = fmax(Ymax, shfl_xor_f64(Ymax, off));
-    }
+    e.wave_reduce();
     if (lane != 0) return;
+    int c = e.cnt, bx0 = e.xmin, by0 = e.ymin, bx1 = e.xmax, by1 = e.ymax;
     if (c < 100) {
         const int lo = 105, hx = min(315, W) - 1, hy = min(315, Hh) - 1;
         if (c == 0) { bx0 = lo; by0 = lo; bx1 = hx; by1 = hy; }
@@ -1040,8 +834,8 @@ __global__ __launch_bounds__(64) void raster_extents_kernel(const double* __rest
     if (ext) {
         double* o = ext + (size_t)v * 8;
         o[0] = (double)bx0; o[1] = (double)by0; o[2] = (double)bx1; o[3] = (double)by1;
-        o[4] = Xmax > -1e299 ? Xmax - Xmin : 0.0;
-        o[5] = Ymax > -1e299 ? Ymax - Ymin : 0.0;
+        o[4] = e.Xmax > -1e299 ? e.Xmax - e.Xmin : 0.0;
+        o[5] = e.Ymax > -1e299 ? e.Ymax - e.Ymin : 0.0;
         o[6] = (double)c; o[7] = 0.0;
     }
     if (boxes) { boxes[4 * v] = bx0; boxes[4 * v + 1] = by0; boxes[4 * v + 2] = bx1; boxes[4 * v + 3] = by1; }
@@ -1068,6 +862,15 @@ __global__ void raster_export_kernel(const SVert* __restrict__ sv, const int32_t
 
 }  // namespace
 
+// device copy of `bytes` bytes of host memory: *dst is allocated here (and freed by fp_mesh_destroy)
+template <class T> static int upload(T** dst, const void* src, size_t bytes) {
+    void* d = nullptr;
+    FP_HIP(hipMalloc(&d, bytes));
+    *dst = (T*)d;                  // (owned by the mesh from here on, also when the copy fails)
+    FP_HIP(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    return FP_OK;
+}
+
 static int mesh_tables(fp_mesh* m) {
     // DEC[i] = sRGB -> linear of i/255 ; THR[k] = ((k - 0.5)/255)^2.2 (THR[0] = 0): double precision, rounded to float once
     float tab[512];
@@ -1076,124 +879,113 @@ static int mesh_tables(fp_mesh* m) {
         tab[i] = (float)(sv <= 0.04045 ? sv / 12.92 : pow((sv + 0.055) / 1.055, 2.4));
         tab[256 + i] = i == 0 ? 0.f : (float)pow(((double)i - 0.5) / 255.0, 2.2);
     }
-    FP_HIP(hipMalloc((void**)&m->tables, sizeof(tab)));
-    FP_HIP(hipMemcpy(m->tables, tab, sizeof(tab), hipMemcpyHostToDevice));
-    return FP_OK;
+    return upload(&m->tables, tab, sizeof(tab));
 }
 
 extern "C" int fp_mesh_destroy(fp_mesh* m);
-namespace {
 // frees a half-built mesh when an upload step fails (FP_HIP / FP_REQUIRE return early); release() on success
-struct MeshGuard {
-    fp_mesh* m;
-    ~MeshGuard() { if (m) (void)fp_mesh_destroy(m); }
-    fp_mesh* release() { fp_mesh* r = m; m = nullptr; return r; }
-};
-}  // namespace
+struct MeshGuard : std::unique_ptr<fp_mesh, int (*)(fp_mesh*)> { explicit MeshGuard(fp_mesh* m) : unique_ptr(m, fp_mesh_destroy) {} };
+
+// slot -> face id: Morton order of the triangle centroids (10 bits per axis over the vertex bounding box), ties by face id
+static std::vector<int32_t> morton_order(const float* h_verts, int V, const int32_t* h_faces, int F) {
+    float lo[3] = {h_verts[0], h_verts[1], h_verts[2]}, hi[3] = {h_verts[0], h_verts[1], h_verts[2]};
+    for (int i = 0; i < V; ++i)
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], h_verts[3 * i + a]); hi[a] = std::max(hi[a], h_verts[3 * i + a]); }
+    auto spread = [](uint32_t x) {   // 10 bits -> every third bit
+        x &= 0x3ffu; x = (x | (x << 16)) & 0x030000ffu; x = (x | (x << 8)) & 0x0300f00fu; x = (x | (x << 4)) & 0x030c30c3u; x = (x | (x << 2)) & 0x09249249u;
+        return x;
+    };
+    std::vector<std::pair<uint32_t, int32_t>> key((size_t)F);
+    for (int f = 0; f < F; ++f) {
+        uint32_t code = 0;
+        for (int a = 0; a < 3; ++a) {
+            const float c = (h_verts[3 * h_faces[3 * f] + a] + h_verts[3 * h_faces[3 * f + 1] + a] + h_verts[3 * h_faces[3 * f + 2] + a]) * (1.0f / 3.0f);
+            const float span = hi[a] - lo[a];
+            float u = span > 0.f ? (c - lo[a]) / span : 0.f;
+            if (!(u >= 0.f)) u = 0.f;                // (NaN vertices land in cell 0; they are dropped by the raster set-up anyway)
+            const uint32_t q = (uint32_t)std::min(1023.0f, u * 1024.0f);
+            code |= spread(q) << a;
+        }
+        key[f] = {code, f};
+    }
+    std::sort(key.begin(), key.end());
+    std::vector<int32_t> perm((size_t)F);
+    for (int f = 0; f < F; ++f) perm[f] = key[f].second;
+    return perm;
+}
+
+// caller's vertex id -> device vertex id: order of first use along the sorted triangles, unreferenced vertices last (fp_mesh::vmap says why)
+static std::vector<int32_t> first_use_order(const std::vector<int32_t>& perm, int V, const int32_t* h_faces) {
+    std::vector<int32_t> vmap((size_t)V, -1);
+    int next = 0;
+    for (const int32_t f : perm)
+        for (int a = 0; a < 3; ++a) { int32_t& id = vmap[h_faces[3 * (size_t)f + a]]; if (id < 0) id = next++; }
+    for (int i = 0; i < V; ++i) if (vmap[i] < 0) vmap[i] = next++;
+    return vmap;
+}
 
 static int mesh_geometry(fp_ctx* ctx, const float* h_verts, int V, const int32_t* h_faces, int F, fp_mesh** out) {
     FP_REQUIRE(ctx && h_verts && h_faces && out && V > 0 && F > 0, "mesh_upload: bad argument");
     for (int i = 0; i < 3 * F; ++i) FP_REQUIRE(h_faces[i] >= 0 && h_faces[i] < V, "mesh_upload: face index out of range");
     fp_mesh* m = new fp_mesh();
-    MeshGuard guard{m};
+    MeshGuard guard(m);
     m->ctx = ctx; m->V = V; m->F = F;
-    FP_HIP(hipMalloc((void**)&m->verts, (size_t)V * 12));
-    FP_HIP(hipMalloc((void**)&m->faces, (size_t)F * 12));
-    {   // Morton order of the triangle centroids (10 bits per axis over the vertex bounding box), ties by face id
-        float lo[3] = {h_verts[0], h_verts[1], h_verts[2]}, hi[3] = {h_verts[0], h_verts[1], h_verts[2]};
-        for (int i = 0; i < V; ++i)
-            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], h_verts[3 * i + a]); hi[a] = std::max(hi[a], h_verts[3 * i + a]); }
-        auto spread = [](uint32_t x) {   // 10 bits -> every third bit
-            x &= 0x3ffu; x = (x | (x << 16)) & 0x030000ffu; x = (x | (x << 8)) & 0x0300f00fu; x = (x | (x << 4)) & 0x030c30c3u; x = (x | (x << 2)) & 0x09249249u;
-            return x;
-        };
-        std::vector<std::pair<uint32_t, int32_t>> key((size_t)F);
-        for (int f = 0; f < F; ++f) {
-            uint32_t code = 0;
-            for (int a = 0; a < 3; ++a) {
-                const float c = (h_verts[3 * h_faces[3 * f] + a] + h_verts[3 * h_faces[3 * f + 1] + a] + h_verts[3 * h_faces[3 * f + 2] + a]) * (1.0f / 3.0f);
-                const float span = hi[a] - lo[a];
-                float u = span > 0.f ? (c - lo[a]) / span : 0.f;
-                if (!(u >= 0.f)) u = 0.f;                // (NaN vertices land in cell 0; they are dropped by the raster set-up anyway)
-                const uint32_t q = (uint32_t)std::min(1023.0f, u * 1024.0f);
-                code |= spread(q) << a;
-            }
-            key[f] = {code, f};
-        }
-        std::sort(key.begin(), key.end());
-        std::vector<int32_t> perm((size_t)F);
-        for (int f = 0; f < F; ++f) perm[f] = key[f].second;
-        // device vertex ids: order of first use along the sorted triangles (unreferenced vertices last).  Purely internal — outputs carry
-        // no vertex id, fp_project_vertices maps back — but a chunk's vertices are then neighbours in the per-view vertex array: the
-        // gathers of the bin / tile / resolve stages fetched one 128-byte line per 16-byte vertex before (3 x 64 lines per chunk).
-        std::vector<int32_t> vmap((size_t)V, -1);
-        int next = 0;
-        for (int k = 0; k < F; ++k)
-            for (int a = 0; a < 3; ++a) { int32_t& id = vmap[h_faces[3 * (size_t)perm[k] + a]]; if (id < 0) id = next++; }
-        for (int i = 0; i < V; ++i) if (vmap[i] < 0) vmap[i] = next++;
-        std::vector<float> verts((size_t)V * 3);
-        for (int i = 0; i < V; ++i)
-            for (int a = 0; a < 3; ++a) verts[3 * (size_t)vmap[i] + a] = h_verts[3 * (size_t)i + a];
-        std::vector<int32_t> faces((size_t)F * 3), fsort((size_t)F * 3);
-        for (size_t i = 0; i < (size_t)F * 3; ++i) faces[i] = vmap[h_faces[i]];
-        for (int k = 0; k < F; ++k)
-            for (int a = 0; a < 3; ++a) fsort[3 * (size_t)k + a] = faces[3 * (size_t)perm[k] + a];
-        FP_HIP(hipMemcpy(m->verts, verts.data(), (size_t)V * 12, hipMemcpyHostToDevice));
-        FP_HIP(hipMemcpy(m->faces, faces.data(), (size_t)F * 12, hipMemcpyHostToDevice));
-        FP_HIP(hipMalloc((void**)&m->perm, (size_t)F * 4));
-        FP_HIP(hipMemcpy(m->perm, perm.data(), (size_t)F * 4, hipMemcpyHostToDevice));
-        FP_HIP(hipMalloc((void**)&m->fsort, (size_t)F * 12));
-        FP_HIP(hipMemcpy(m->fsort, fsort.data(), (size_t)F * 12, hipMemcpyHostToDevice));
-        FP_HIP(hipMalloc((void**)&m->vmap, (size_t)V * 4));
-        FP_HIP(hipMemcpy(m->vmap, vmap.data(), (size_t)V * 4, hipMemcpyHostToDevice));
-        m->h_vmap = std::move(vmap);
-    }
-    int rc = mesh_tables(m);
-    if (rc) return rc;
+    const std::vector<int32_t> perm = morton_order(h_verts, V, h_faces, F);
+    std::vector<int32_t> vmap = first_use_order(perm, V, h_faces);
+    std::vector<float> verts((size_t)V * 3);
+    for (int i = 0; i < V; ++i)
+        for (int a = 0; a < 3; ++a) verts[3 * (size_t)vmap[i] + a] = h_verts[3 * (size_t)i + a];
+    std::vector<int32_t> faces((size_t)F * 3), fsort((size_t)F * 3);
+    for (size_t i = 0; i < (size_t)F * 3; ++i) faces[i] = vmap[h_faces[i]];
+    for (int k = 0; k < F; ++k)
+        for (int a = 0; a < 3; ++a) fsort[3 * (size_t)k + a] = faces[3 * (size_t)perm[k] + a];
+    int rc;
+    if ((rc = upload(&m->verts, verts.data(), (size_t)V * 12)) || (rc = upload(&m->faces, faces.data(), (size_t)F * 12)) ||
+        (rc = upload(&m->perm, perm.data(), (size_t)F * 4)) || (rc = upload(&m->fsort, fsort.data(), (size_t)F * 12)) ||
+        (rc = upload(&m->vmap, vmap.data(), (size_t)V * 4)) || (rc = mesh_tables(m)))
+        return rc;
+    m->h_vmap = std::move(vmap);
     *out = guard.release();
     return FP_OK;
 }
 
-extern "C" int fp_mesh_upload(fp_ctx* ctx, const float* h_verts, int V, const int32_t* h_faces, int F,
-                              const uint8_t* h_colors, fp_mesh** out) {
+extern "C" int fp_mesh_upload(fp_ctx* ctx, const float* h_verts, int V, const int32_t* h_faces, int F, const uint8_t* h_colors, fp_mesh** out) {
     fp_mesh* m = nullptr;
     int rc = mesh_geometry(ctx, h_verts, V, h_faces, F, &m);
     if (rc) return rc;
-    MeshGuard guard{m};
+    MeshGuard guard(m);
     if (h_colors) {
         std::vector<uint8_t> rgba((size_t)V * 4, 255);
         for (int i = 0; i < V; ++i) {
             const size_t d = (size_t)m->h_vmap[i];                   // vertex attributes live at the device id
             rgba[4 * d] = h_colors[3 * i]; rgba[4 * d + 1] = h_colors[3 * i + 1]; rgba[4 * d + 2] = h_colors[3 * i + 2];
         }
-        FP_HIP(hipMalloc((void**)&m->colors, (size_t)V * 4));
-        FP_HIP(hipMemcpy(m->colors, rgba.data(), (size_t)V * 4, hipMemcpyHostToDevice));
+        if ((rc = upload(&m->sh.colors, rgba.data(), (size_t)V * 4))) return rc;
     }
     *out = guard.release();
     return FP_OK;
 }
 
 extern "C" int fp_mesh_upload_textured(fp_ctx* ctx, const float* h_verts, int V, const int32_t* h_faces, int F,
-                                       const float* h_uv, const uint8_t* h_texture, int th, int tw, const float* h_kd3,
-                                       fp_mesh** out) {
+                                       const float* h_uv, const uint8_t* h_texture, int th, int tw, const float* h_kd3, fp_mesh** out) {
     FP_REQUIRE(h_uv && h_texture && th > 0 && tw > 0 && th <= 16384 && tw <= 16384, "mesh_upload_textured: bad texture argument");
     fp_mesh* m = nullptr;
     int rc = mesh_geometry(ctx, h_verts, V, h_faces, F, &m);
     if (rc) return rc;
-    MeshGuard guard{m};
+    MeshGuard guard(m);
     // level 0 + the box-filtered chain down to 1 x 1 (contract in the header), rgba, back to back
     int lw[16], lh[16], n = 0;
     size_t total = 0;
     for (int w = tw, h = th;; w = w > 1 ? w >> 1 : 1, h = h > 1 ? h >> 1 : 1) {
-        lw[n] = w; lh[n] = h; m->lev_off[n] = (uint32_t)total; total += (size_t)w * h; ++n;
+        lw[n] = w; lh[n] = h; m->sh.lev_off[n] = (uint32_t)total; total += (size_t)w * h; ++n;
         if ((w == 1 && h == 1) || n == 16) break;
     }
-    m->nlev = n;
+    m->sh.nlev = n;
     std::vector<uint8_t> rgba(total * 4, 255);
     for (size_t i = 0; i < (size_t)th * tw; ++i) { rgba[4 * i] = h_texture[3 * i]; rgba[4 * i + 1] = h_texture[3 * i + 1]; rgba[4 * i + 2] = h_texture[3 * i + 2]; }
     for (int k = 1; k < n; ++k) {
-        const uint8_t* src = rgba.data() + (size_t)m->lev_off[k - 1] * 4;
-        uint8_t* dst = rgba.data() + (size_t)m->lev_off[k] * 4;
+        const uint8_t* src = rgba.data() + (size_t)m->sh.lev_off[k - 1] * 4;
+        uint8_t* dst = rgba.data() + (size_t)m->sh.lev_off[k] * 4;
         const int sw = lw[k - 1], sh = lh[k - 1];
         for (int y = 0; y < lh[k]; ++y)
             for (int x = 0; x < lw[k]; ++x) {
@@ -1203,38 +995,30 @@ extern "C" int fp_mesh_upload_textured(fp_ctx* ctx, const float* h_verts, int V,
                                                                      src[((size_t)y1 * sw + x0) * 4 + c] + src[((size_t)y1 * sw + x1) * 4 + c] + 2) >> 2);
             }
     }
-    FP_HIP(hipMalloc((void**)&m->tex, rgba.size()));
-    FP_HIP(hipMemcpy(m->tex, rgba.data(), rgba.size(), hipMemcpyHostToDevice));
-    FP_HIP(hipMalloc((void**)&m->uv, (size_t)F * 24));
-    FP_HIP(hipMemcpy(m->uv, h_uv, (size_t)F * 24, hipMemcpyHostToDevice));
-    m->th = th; m->tw = tw;
-    if (h_kd3) { m->kd[0] = h_kd3[0]; m->kd[1] = h_kd3[1]; m->kd[2] = h_kd3[2]; }
+    if ((rc = upload(&m->sh.tex, rgba.data(), rgba.size())) || (rc = upload(&m->sh.uv, h_uv, (size_t)F * 24))) return rc;
+    m->sh.th = th; m->sh.tw = tw;
+    if (h_kd3) { m->sh.kd0 = h_kd3[0]; m->sh.kd1 = h_kd3[1]; m->sh.kd2 = h_kd3[2]; }
     *out = guard.release();
     return FP_OK;
 }
 extern "C" int fp_mesh_destroy(fp_mesh* m) {
     if (!m) return FP_OK;
-    if (m->verts) (void)hipFree(m->verts);
-    if (m->faces) (void)hipFree(m->faces);
-    if (m->perm) (void)hipFree(m->perm);
-    if (m->fsort) (void)hipFree(m->fsort);
-    if (m->vmap) (void)hipFree(m->vmap);
-    if (m->colors) (void)hipFree(m->colors);
-    if (m->uv) (void)hipFree(m->uv);
-    if (m->tex) (void)hipFree(m->tex);
-    if (m->tables) (void)hipFree(m->tables);
+    for (void* p : {(void*)m->verts, (void*)m->faces, (void*)m->perm, (void*)m->fsort, (void*)m->vmap, (void*)m->sh.colors, (void*)m->sh.uv,
+                    (void*)m->sh.tex, (void*)m->tables})
+        if (p) (void)hipFree(p);
     delete m;
     return FP_OK;
 }
 
-static ShadeArgs shade_args(const fp_mesh* m) {
-    ShadeArgs a;
-    a.colors = m->colors; a.uv = m->uv; a.tex = m->tex; a.th = m->th; a.tw = m->tw;
-    a.kd0 = m->kd[0]; a.kd1 = m->kd[1]; a.kd2 = m->kd[2];
-    a.ambient = m->ambient; a.shade = m->shade;
-    a.nlev = m->nlev; a.filter = m->filter;
-    for (int k = 0; k < 16; ++k) a.lev_off[k] = m->lev_off[k];
-    return a;
+// vertex stage of Hn views into the context's "raster.sv" ([Hn, V] SVert, device vertex ids)
+static int project_views(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses, int Hn, float scale, float fx, float fy, float cx, float cy,
+                         hipStream_t s, SVert** sv) {
+    const int V = mesh->V;
+    int rc;
+    if ((rc = ctx->get("raster.sv", (size_t)Hn * V * sizeof(SVert), (void**)sv))) return rc;
+    hipLaunchKernelGGL(raster_vertex_kernel, dim3(cdiv(V, 256), Hn), dim3(256), 0, s, mesh->verts, V, d_poses, Hn, scale, fx, fy, cx, cy, *sv);
+    FP_LAUNCH_CHECK();
+    return FP_OK;
 }
 
 extern "C" int fp_project_vertices(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses, int Hn, float scale, float fx,
@@ -1242,15 +1026,11 @@ extern "C" int fp_project_vertices(fp_ctx* ctx, const fp_mesh* mesh, const float
     FP_REQUIRE(ctx && mesh && d_poses && d_xy && d_zc, "project_vertices: null argument");
     if (Hn == 0) return FP_OK;
     hipStream_t s = (hipStream_t)stream;
-    const int V = mesh->V;
     SVert* sv;
     int rc;
-    if ((rc = ctx->get("raster.sv", (size_t)Hn * V * sizeof(SVert), (void**)&sv))) return rc;
-    hipLaunchKernelGGL(raster_vertex_kernel, dim3(cdiv(V, 256), Hn), dim3(256), 0, s, mesh->verts, V, d_poses, Hn, scale,
-                       fx, fy, cx, cy, sv);
-    FP_LAUNCH_CHECK();
-    const size_t n = (size_t)Hn * V;
-    hipLaunchKernelGGL(raster_export_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sv, mesh->vmap, V, n, d_xy, d_zc);
+    if ((rc = project_views(ctx, mesh, d_poses, Hn, scale, fx, fy, cx, cy, s, &sv))) return rc;
+    const size_t n = (size_t)Hn * mesh->V;
+    hipLaunchKernelGGL(raster_export_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sv, mesh->vmap, mesh->V, n, d_xy, d_zc);
     FP_LAUNCH_CHECK();
     return FP_OK;
 }
@@ -1261,14 +1041,10 @@ static int rasterize_impl(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses
     const int V = mesh->V, F = mesh->F;
     SVert* sv;
     int rc;
-    if ((rc = ctx->get("raster.sv", (size_t)Hn * V * sizeof(SVert), (void**)&sv))) return rc;
-    hipLaunchKernelGGL(raster_vertex_kernel, dim3(cdiv(V, 256), Hn), dim3(256), 0, s, mesh->verts, V, d_poses, Hn, scale,
-                       fx, fy, cx, cy, sv);
-    FP_LAUNCH_CHECK();
+    if ((rc = project_views(ctx, mesh, d_poses, Hn, scale, fx, fy, cx, cy, s, &sv))) return rc;
     const bool want_ext = d_ext || d_boxes;
 
-    // The launch arithmetic is fp_raster::make_plan (raster_plan.h): tile edge 64 px up to 512-px images, else the smallest multiple of
-    // 8 that covers the image with 8 x 8 tiles.
+    // The launch arithmetic is fp_raster::make_plan (raster_plan.h).
     // fp_ctx_set_option(ctx, "raster_tiled", v): -1 / unset = tiled for images of up to 8 x 8 tiles of <= 88 px and meshes of up to
     // 131 072 triangles, 0 = global visibility buffer, 1 = tiled.  Measured, 576 views @420^2 with boxes + extents (ms; tiled | global,
     // profiles/r06_raster_perf.log): 1 280 triangles 1.64 | 2.57, 20 480: 1.65 | 2.70, 81 920: 2.28 | 2.40, 327 680: 5.04 | 2.81 —
@@ -1287,17 +1063,16 @@ static int rasterize_impl(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses
                            nchunk, tbox, cmask, mesh->cull);
         FP_LAUNCH_CHECK();
         unsigned long long* dbg_buf = nullptr;
+        int raster_dbg = 0;
 #ifdef FP_LAB
-        const int raster_dbg = fp_opt_get(FP_OPT_RASTER_DBG, 0);
+        raster_dbg = fp_opt_get(FP_OPT_RASTER_DBG, 0);
         if (raster_dbg & (1 << 30)) {                      // phase clocks: summed over all workgroups into "raster.dbg" (fp_lab_read_buffer)
             if ((rc = ctx->get("raster.dbg", 64, (void**)&dbg_buf))) return rc;
             FP_HIP(hipMemsetAsync(dbg_buf, 0, 64, s));
         }
-#else
-        const int raster_dbg = 0;
 #endif
         FP_DYN_LDS_ONCE(raster_tile_kernel, (int)fp_raster::tile_lds(fp_raster::TILE_MAX));
-        hipLaunchKernelGGL(raster_tile_kernel, dim3(ntile, Hn), dim3(256), plan.lds, s, sv, mesh->faces, mesh->perm, mesh->fsort, shade_args(mesh), mesh->tables,
+        hipLaunchKernelGGL(raster_tile_kernel, dim3(ntile, Hn), dim3(256), plan.lds, s, sv, mesh->faces, mesh->perm, mesh->fsort, mesh->sh, mesh->tables,
                            V, F, W, Hh, T, ntx, Hn, tbox, cmask, nchunk, d_rgb, d_depth, part, (double)fx, (double)fy, (double)cx, (double)cy, raster_dbg & ~(1 << 30), dbg_buf);
         FP_LAUNCH_CHECK();
         if (want_ext) {
@@ -1317,12 +1092,11 @@ static int rasterize_impl(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses
     int* qcount = queue + 2 * qcap;
     FP_HIP(hipMemsetAsync(zb, 0xff, (size_t)Hn * W * Hh * 8, s));
     FP_HIP(hipMemsetAsync(qcount, 0, 4, s));
-    hipLaunchKernelGGL(raster_tri_kernel, dim3(cdiv(F, 256), Hn), dim3(256), 0, s, sv, mesh->faces, mesh->perm, V, F, W, Hh, zb,
-                       queue, qcount, qcap, mesh->cull);
+    hipLaunchKernelGGL(raster_tri_kernel, dim3(cdiv(F, 256), Hn), dim3(256), 0, s, sv, mesh->faces, mesh->perm, V, F, W, Hh, zb, queue, qcount, qcap, mesh->cull);
     FP_LAUNCH_CHECK();
     hipLaunchKernelGGL(raster_big_kernel, dim3(1024), dim3(256), 0, s, sv, mesh->faces, V, W, Hh, zb, queue, qcount, qcap);
     FP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(raster_resolve_kernel, dim3(cdiv(W * Hh, 256), Hn), dim3(256), 0, s, sv, mesh->faces, shade_args(mesh),
+    hipLaunchKernelGGL(raster_resolve_kernel, dim3(cdiv(W * Hh, 256), Hn), dim3(256), 0, s, sv, mesh->faces, mesh->sh,
                        mesh->tables, V, W, Hh, zb, d_rgb, d_depth);
     FP_LAUNCH_CHECK();
     if (want_ext) {
@@ -1337,20 +1111,23 @@ static int rasterize_impl(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses
     return FP_OK;
 }
 
+static int check_raster_args(const char* who, const void* ctx, const void* mesh, const void* d_poses, const void* d_rgb, bool outputs, int W, int Hh) {
+    FP_REQUIRE(ctx && mesh && d_poses && d_rgb && outputs, "%s: null argument", who);
+    FP_REQUIRE(W > 0 && Hh > 0 && W <= 8192 && Hh <= 8192, "%s: bad image size", who);
+    return FP_OK;
+}
+
 extern "C" int fp_rasterize(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses, int Hn, float scale, float fx,
                             float fy, float cx, float cy, int W, int Hh, uint8_t* d_rgb, float* d_depth, void* stream) {
-    FP_REQUIRE(ctx && mesh && d_poses && d_rgb && d_depth, "rasterize: null argument");
-    FP_REQUIRE(W > 0 && Hh > 0 && W <= 8192 && Hh <= 8192, "rasterize: bad image size");
-    if (Hn == 0) return FP_OK;
+    const int rc = check_raster_args("rasterize", ctx, mesh, d_poses, d_rgb, d_depth != nullptr, W, Hh);
+    if (rc || Hn == 0) return rc;
     return rasterize_impl(ctx, mesh, d_poses, Hn, scale, fx, fy, cx, cy, W, Hh, d_rgb, d_depth, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int fp_rasterize_extents(fp_ctx* ctx, const fp_mesh* mesh, const float* d_poses, int Hn, float scale, float fx,
-                                    float fy, float cx, float cy, int W, int Hh, uint8_t* d_rgb, float* d_depth, double* d_ext,
-                                    int32_t* d_boxes, void* stream) {
-    FP_REQUIRE(ctx && mesh && d_poses && d_rgb && (d_ext || d_boxes), "rasterize_extents: null argument");
-    FP_REQUIRE(W > 0 && Hh > 0 && W <= 8192 && Hh <= 8192, "rasterize_extents: bad image size");
-    if (Hn == 0) return FP_OK;
+                                    float fy, float cx, float cy, int W, int Hh, uint8_t* d_rgb, float* d_depth, double* d_ext, int32_t* d_boxes, void* stream) {
+    const int rc = check_raster_args("rasterize_extents", ctx, mesh, d_poses, d_rgb, d_ext || d_boxes, W, Hh);
+    if (rc || Hn == 0) return rc;
     return rasterize_impl(ctx, mesh, d_poses, Hn, scale, fx, fy, cx, cy, W, Hh, d_rgb, d_depth, d_ext, d_boxes, (hipStream_t)stream);
 }
 
@@ -1367,7 +1144,7 @@ extern "C" int fp_op_raster_plan(fp_ctx* ctx, int W, int H, int F, int Hn, char*
 
 extern "C" int fp_mesh_set_ambient(fp_mesh* mesh, float ambient) {
     FP_REQUIRE(mesh && ambient >= 0.f, "mesh_set_ambient: bad argument");
-    mesh->ambient = ambient;
+    mesh->sh.ambient = ambient;
     return FP_OK;
 }
 extern "C" int fp_mesh_set_cull(fp_mesh* mesh, int mode) {
@@ -1377,11 +1154,11 @@ extern "C" int fp_mesh_set_cull(fp_mesh* mesh, int mode) {
 }
 extern "C" int fp_mesh_set_filter(fp_mesh* mesh, int mode) {
     FP_REQUIRE(mesh && (mode == 0 || mode == 1), "mesh_set_filter: mode must be 0 (bilinear level 0) or 1 (trilinear mip-maps)");
-    mesh->filter = mode;
+    mesh->sh.filter = mode;
     return FP_OK;
 }
 extern "C" int fp_mesh_set_shading(fp_mesh* mesh, int mode) {
     FP_REQUIRE(mesh && (mode == 0 || mode == 1), "mesh_set_shading: mode must be 0 (linear) or 1 (gamma)");
-    mesh->shade = mode;
+    mesh->sh.shade = mode;
     return FP_OK;
 }

@@ -12,7 +12,7 @@ Known answer (known_answer): pixel centre (256 px + 128, 256 py + 128), the thre
 the top-left rule on zeros, the nearest plane wins, equal planes go to the lower face id.  It never calls the oracle and shares no code with
 it.  Near-plane straddlers have no integer answer; the cases that hold them are compared with the oracle only (Case.known False).
 
-classify() restates tri_setup_v (csrc/raster.hip) on the integers for every triangle and view and, with plan() — the mirror of
+classify() restates tri_setup_v (csrc/raster_core.h) on the integers for every triangle and view and, with plan() — the mirror of
 csrc/raster_plan.h make_plan — gives the set of branch LABELS a case reaches.  The thresholds are read from raster_plan.h itself
 (CONSTANTS), never copied: the GPU test holds them to the ones the library was compiled with (ops.raster_plan)."""
 from __future__ import annotations
@@ -122,7 +122,7 @@ def launch_labels(W, H, F, Hn, mode):
     return out
 
 
-# ---- tri_setup_v on integers, vectorised over triangles ------------------------------------------------------------------------------------
+# ---- tri_setup_v on integers, vectorised over triangles (held to csrc/raster_core.h by tools/raster_core_host_check.cpp in the CPU test) -------
 @dataclass
 class Setup:
     W: int
@@ -143,7 +143,7 @@ class Setup:
 
 
 def setup(xi, yi, zc, W, H, cull=0):
-    """xi, yi int [F,3] (fixed-point window coordinates, already clamped), zc float [F,3] -> Setup (raster.hip tri_setup_v)"""
+    """xi, yi int [F,3] (fixed-point window coordinates, already clamped), zc float [F,3] -> Setup (raster_core.h tri_setup_v)"""
     xi, yi = np.asarray(xi, np.int64), np.asarray(yi, np.int64)
     front = np.asarray(zc, np.float32) > np.float32(ZNEAR)
     nfront = front.sum(1)
@@ -279,7 +279,7 @@ def shifted(case, view):
 
 
 def projected(case, view):
-    """what the vertex stage must produce: shifted(), clamped to +-CLAMP_PX px (raster_vertex_kernel)"""
+    """what the vertex stage must produce: shifted(), clamped to +-CLAMP_PX px (raster_core.h project_vertex)"""
     xs, ys, zc = shifted(case, view)
     lim = CLAMP_PX * 256
     return np.clip(xs, -lim, lim), np.clip(ys, -lim, lim), zc

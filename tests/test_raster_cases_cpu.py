@@ -161,6 +161,56 @@ def test_plan_mirror_on_a_sweep(plan_check):
             documented["flush"]) == ("tiled", 80, (8, 1), 5, 1, (1, 3), "dword")
 
 
+# ---- the library's own statement of the triangle set-up (csrc/raster_core.h) against the mirror ------------------------------------------------
+@pytest.fixture(scope="module")
+def core_check(tmp_path_factory):
+    """tools/raster_core_host_check.cpp under the host sanitizers: rows [W, H, cull, x0, y0, z0, x1, y1, z1, x2, y2, z2] -> int array
+    [n, 10] (ok, strad, swapped, area2, bx0, by0, bx1, by1, small, back_facing) of tri_setup_v; exit status 0 covers its own sweeps of the
+    header's arithmetic claims (row / column split, 32-bit == 64-bit edge functions, reciprocal == quotient, key order), and the sanitizers"""
+    gxx = shutil.which("g++")
+    assert gxx, "g++ not found"
+    exe = tmp_path_factory.mktemp("raster_core") / "raster_core_host_check"
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", str(ROOT / "freepose_amd" / "csrc"),
+           str(ROOT / "tools" / "raster_core_host_check.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+    def run(rows):
+        text = "".join("%d %d %d %d %d %.9g %d %d %.9g %d %d %.9g\n" % tuple(row) for row in rows)
+        r = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+        out = np.array(r.stdout.split(), dtype=np.int64).reshape(-1, 10)
+        assert len(out) == len(rows)
+        return out
+    return run
+
+
+def test_setup_of_every_case_is_the_headers(core_check):
+    """every triangle of every view of every case: tri_setup_v of csrc/raster_core.h, run on the CPU, against the mirror setup().  For a
+    near-plane straddler set-up stores area2 = 1 (nothing reads it) where the mirror keeps the integer area, and the mirror does not judge
+    its facing: area2 is held to 1 there, `culled` compared on the other triangles only."""
+    rows, mirrors = [], []
+    for c in rc.CASES:
+        for view in range(c.Hn):
+            xi, yi, zc = rc.projected(c, view)
+            z32 = zc.astype(np.float32).astype(np.float64)
+            head = np.broadcast_to(np.array([c.W, c.H, c.cull], np.float64), (len(xi), 3))
+            rows.append(np.concatenate([head] + [np.stack([xi[:, k], yi[:, k], z32[:, k]], 1) for k in range(3)], 1))
+            mirrors.append((c, view, rc.setup(xi, yi, zc, c.W, c.H, c.cull)))
+    got = core_check(np.concatenate(rows))
+    at = 0
+    for c, view, s in mirrors:
+        g = got[at:at + len(s.ok)]
+        at += len(s.ok)
+        where = (c.name, view)
+        assert np.array_equal(g[:, 0], s.ok) and np.array_equal(g[:, 1], s.strad) and np.array_equal(g[:, 2], s.swapped), where
+        assert np.array_equal(g[:, 3], np.where(s.strad, 1, s.area2)), where
+        assert np.array_equal(g[:, 4:8], s.bbox) and np.array_equal(g[:, 8], s.small), where
+        plain = ~s.strad
+        assert np.array_equal((g[:, 0] & g[:, 9] & c.cull)[plain], s.culled[plain]), where
+    assert at == len(got)
+
+
 # ---- the ledger -------------------------------------------------------------------------------------------------------------------------------
 def _fuzz_scenes():
     """the twelve rasteriser scenes of tests/test_gpu_fuzz.py (6 vertex-coloured soups, 6 textured ones), their geometry regenerated by the

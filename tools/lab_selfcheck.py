@@ -131,6 +131,35 @@ def main():
     ops.set_option("gemm_dbg", -1)
     torch.cuda.synchronize()
     assert (outb == 7.0).all(), "gemm_dbg = 8 (no epilogue) still wrote the output"
+    # 5. rasteriser: the tile kernel's lab hooks (tools/raster_ablate.py).  One constructed case with triangles on both sides of the
+    #    32-candidate threshold: the threshold option only moves triangles between the per-lane and the whole-wave routine, the phase clocks
+    #    do not touch the picture -> the oracle's bytes every time; the clocks of all five phases tick.  (The ablation bits 1 / 2 / 4 / 8
+    #    give wrong pictures by design and are not run.)
+    import ctypes as C
+    import numpy as np
+    from tests import _raster_cases as rc
+    case = rc.BY_NAME["tile-candidates-96x80"]
+    assert (case.W, case.H) == (96, 80)
+    mesh = ops.Mesh(*rc.mesh(case)).set_shading(0).set_ambient(1.0).set_cull(case.cull)
+    poses = torch.from_numpy(rc.poses(case))
+    rgb_o, d_o = rc.oracle_render(case)
+    lib = _lib.load()
+    lib.fp_lab_read_buffer.restype = C.c_int
+    lib.fp_lab_read_buffer.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]
+    ops.set_option("raster_tiled", 1)
+    try:
+        for dbg in (0, 1 << 8, 8 << 8, 32 << 8, 1 << 30):
+            ops.set_option("raster_dbg", dbg)
+            rgb, depth = ops.rasterize(mesh, poses, 1.0, *rc.intrinsics(case), case.W, case.H)
+            assert np.array_equal(depth.cpu().numpy().view(np.uint32), d_o.view(np.uint32)), f"raster_dbg {dbg}: depth differs from the oracle"
+            assert np.array_equal(rgb.cpu().numpy(), rgb_o), f"raster_dbg {dbg}: colours differ from the oracle"
+            if dbg & (1 << 30):
+                clocks = (C.c_ulonglong * 8)()
+                _lib.check(lib.fp_lab_read_buffer(ops.context(), b"raster.dbg", clocks, 64), "fp_lab_read_buffer")
+                assert all(clocks[k] > 0 for k in range(5)), f"phase clocks (init, mask scan, chunk loop, resolve, flush): {list(clocks)[:5]}"
+    finally:
+        ops.set_option("raster_dbg", 0)
+        ops.set_option("raster_tiled", -1)
     print("LAB_SELFCHECK_OK")
 
 
