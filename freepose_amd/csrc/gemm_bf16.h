@@ -3,6 +3,7 @@
 // W keeps the torch nn.Linear layout ([out,in]) so a DINOv2 state-dict tensor is used as-is.
 #pragma once
 #include "common.h"
+#include "gemm_core.h"
 #include "gemm_plan.h"
 
 // enum FpGemmEpi (the epilogues) lives in gemm_plan.h, beside the dispatch policy that reads it
@@ -86,47 +87,28 @@ __device__ __forceinline__ void fp_ln_finalize_row(const float2* __restrict__ pa
     rec = fp_ln_row_record(mean, sigma);
     rstd = __builtin_amdgcn_rcpf(sigma);
 }
+// Prologue of the small tile tiers (gemm_bf16.hip, gemm_asm.hip) when the row statistics arrive as partial sums (FpGemmArgs::ln_part): the
+// ROWS rows of the tile at m0 are finalised by the workgroup's THREADS threads and written where the init records and the epilogue (and the
+// V^T launch that follows on the stream) read them.  Every workgroup of a row block writes the same bits.
+template <int ROWS, int THREADS>
+__device__ __forceinline__ void fp_gemm_finalize_tile_rows(const FpGemmArgs& p, int m0, int tid) {
+    if (p.ln_part) {
+        for (int r = tid; r < ROWS; r += THREADS) {
+            const int row = m0 + r;
+            if (row < p.M) {
+                uint4 rec;
+                float rstd;
+                fp_ln_finalize_row(p.ln_part, (size_t)p.ln_part_ld, p.ln_part_nb, row, p.ln_inv_d, p.ln_eps, rec, rstd);
+                p.ln_mfrag[row] = rec;
+                p.ln_rstd[row] = rstd;
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
 
-// Tile order shared by the GEMM kernels.  blockIdx -> logical id (XCD-contiguous, bijective) -> (tile_m, tile_n) in
-// column STRIPS of 4 n-tiles swept m-major: the 32 tiles an XCD runs concurrently then cover 8 X row-panels x 4 W
-// panels, so a strip's W slabs (<= 2 MB) stay in the XCD's 4 MB L2 for the whole sweep and each X panel is fetched once
-// per strip.  (rocprofv3, fc1 with N = 4096: the plain row-major order streamed the 8 MB weight matrix once per 2
-// row-panels — FETCH_SIZE 9x the algorithmic bytes.)
-// blockIdx -> logical id: workgroups are dealt to the 8 XCDs round-robin; the remap gives each XCD a CONTIGUOUS run of logical ids
-__device__ __forceinline__ int fp_gemm_xcd_remap(int block, int nblocks) {
-    const int q = nblocks >> 3, r = nblocks & 7, xcd = block & 7, pos = block >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-}
-// logical tile id -> (tile_m, tile_n) in column strips of SW n-tiles swept m-major
-template <int SW = 4>
-__device__ __forceinline__ void fp_gemm_tile_of_id(int id, int tiles_m, int tiles_n, int& tm, int& tn) {
-    const int full = tiles_n / SW, tail = tiles_n - full * SW;
-    const int in_full = full * tiles_m * SW;
-    if (id < in_full) {
-        const int strip = id / (tiles_m * SW), rem = id - strip * (tiles_m * SW);
-        tm = rem / SW;
-        tn = strip * SW + (rem - tm * SW);
-    } else {
-        const int rem = id - in_full;
-        tm = rem / tail;
-        tn = full * SW + (rem - tm * tail);
-    }
-}
-template <int SW = 4>
-__device__ __forceinline__ void fp_gemm_tile(int block, int nblocks, int tiles_m, int tiles_n, int& tm, int& tn) {
-    const int id = fp_gemm_xcd_remap(block, nblocks);
-    const int full = tiles_n / SW, tail = tiles_n - full * SW;
-    const int in_full = full * tiles_m * SW;
-    if (id < in_full) {
-        const int strip = id / (tiles_m * SW), rem = id - strip * (tiles_m * SW);
-        tm = rem / SW;
-        tn = strip * SW + (rem - tm * SW);
-    } else {
-        const int rem = id - in_full;
-        tm = rem / tail;
-        tn = full * SW + (rem - tm * tail);
-    }
-}
+// (the tile order shared by the GEMM kernels — fp_gemm_xcd_remap, fp_gemm_tile_of_id, fp_gemm_tile — lives in gemm_core.h)
 
 // Launch on `stream`. Returns FP_OK / error code (fp_last_error() has the text).
 int fp_gemm_bf16(const FpGemmArgs& a, int epi, hipStream_t stream);

@@ -198,7 +198,7 @@ struct AgprAcc {
 //            lane's 32 B into the slab (row li; 16-B slots XOR-swizzled with (row>>1)&7 like the operand tiles);
 //   phase 2 (row layout: 8 lanes x 16 B = one full 128-B output row, 8 rows per instruction): read back, apply
 //            LayerScale+residual / position embedding with equally coalesced loads, store.
-// Full rows are what allows STREAMING stores (VAR bit 64, used by the big-tile kernels whose outputs are far larger than
+// Full rows are what allows STREAMING stores (fp_gemm::V_STREAM_IO, used by the big-tile kernels whose outputs are far larger than
 // L2 + MALL): measured (profiles/r01_ab.md) the write-back tail of plain stores cost 10-25 % of each GEMM — every tile
 // round dirties the whole L2 and the next round stalls on its eviction — while non-temporal full-line stores bring the
 // bias-only GEMM to the vendor library's epilogue-free time.  From the accumulator layout (16 lines per 16-lane pass)
@@ -235,13 +235,13 @@ __device__ __forceinline__ void epilogue_acc(const FpGemmArgs& p, const Acc& acc
         const int lane = lg * 16 + li;
         const int prow = lane >> 3, pslot = lane & 7;           // phase-2 role: row inside an 8-row half, 16-B column chunk
         char* wr = stg + li * 128;
-        const int wkey = (li >> 1) & 7;
+        const int wkey = key_plain(li);                        // slab_addr(li, slot) = wr + ((slot ^ wkey) << 4)
         const int mbase = m0 + wm * (16 * TM);
         // Output stores and residual loads go through buffer descriptors clipped at row M (an out-of-range offset is dropped / reads
         // zero) and a lane whose 8 columns lie past N gets an offset past every range: no bounds branch, no 64-bit address arithmetic
         // per access (a fifth of the plain epilogue's vector-ALU instructions).  The patch scatter keeps pointers (rows move per crop).
         constexpr bool BUF = EPI != FP_EPI_PATCH;
-        constexpr int AUX = (VAR & 64) ? 2 : 0;                 // streaming (non-temporal) policy of the big-tile kernels
+        constexpr int AUX = stream_io(VAR) ? 2 : 0;                 // streaming (non-temporal) policy of the big-tile kernels
         const int rows_left = max(p.M - mbase, 0);
         auto records = [&](int ld) { const unsigned long long bb = (unsigned long long)rows_left * (unsigned)ld * 2ull; return (int)(bb > 0x7fffffffull ? 0x7fffffffull : bb); };
         __amdgpu_buffer_rsrc_t rsC, rsR;
@@ -296,7 +296,7 @@ __device__ __forceinline__ void epilogue_acc(const FpGemmArgs& p, const Acc& acc
                     for (int e = 0; e < 16; ++e) v[e] *= rs[i];
                 }
                 u32x4_t w0, w1;                                  // bf16 rounding point of the linear layer (/ GELU) output
-                if constexpr (EGELU && (VAR & 4) != 0) {
+                if constexpr (EGELU && table_gelu(VAR)) {
                     uint32_t g[8];
                     gelu_tab16(v, g, gelu_tab);
                     w0 = u32x4_t{g[0], g[1], g[2], g[3]};
@@ -318,7 +318,7 @@ __device__ __forceinline__ void epilogue_acc(const FpGemmArgs& p, const Acc& acc
                 for (int h = 0; h < 2; ++h) {
                     const int r = h * 8 + prow;
                     const u32x4_t t = __builtin_bit_cast(
-                        u32x4_t, *(const bf16x8_t*)(stg + r * 128 + ((pslot ^ ((r >> 1) & 7)) << 4)));
+                        u32x4_t, *(const bf16x8_t*)(stg + r * 128 + ((pslot ^ key_plain(r)) << 4)));
                     const int m = mbase + 16 * i + r;
                     if constexpr (!BUF) {
                         if (m >= p.M || nb2 >= p.N) continue;
@@ -366,7 +366,7 @@ __device__ __forceinline__ void epilogue_acc(const FpGemmArgs& p, const Acc& acc
                     }
                     if (FP_GEMM_DBG_BIT(p, 16) && o.x != 0x12345678u) continue;   // lab build only (gemm_dbg = 16): everything but the stores
                     if constexpr (BUF) __builtin_amdgcn_raw_buffer_store_b128(o, rsC, col_ok ? (16 * i + r) * ldc2 + nb2 * 2 : 0x7fffffff, 0, AUX);
-                    else if constexpr ((VAR & 64) != 0) __builtin_nontemporal_store(o, (u32x4_t*)(p.C + orow * p.ldc + nb2));
+                    else if constexpr (stream_io(VAR)) __builtin_nontemporal_store(o, (u32x4_t*)(p.C + orow * p.ldc + nb2));
                     else *(u32x4_t*)(p.C + orow * p.ldc + nb2) = o;
                 }
             });
@@ -380,7 +380,7 @@ __device__ __forceinline__ void epilogue_acc(const FpGemmArgs& p, const Acc& acc
         const int lane = lg * 16 + li;
         const int prow = lane >> 3, pslot = lane & 7;
         char* wr = stg + li * 128;
-        const int wkey = (li >> 1) & 7;
+        const int wkey = key_plain(li);                        // slab_addr(li, slot) = wr + ((slot ^ wkey) << 4)
         const int m2 = m0 + wm * (16 * TM) + pslot * 8;        // phase-2 tokens of this lane (first of 8)
         const int b2 = m2 / p.npad, t2 = m2 - b2 * p.npad;
         float rt[LNF ? 16 : 1];                                // rstd of this lane's 16 consecutive tokens
@@ -419,11 +419,11 @@ __device__ __forceinline__ void epilogue_acc(const FpGemmArgs& p, const Acc& acc
             for (int h = 0; h < 2; ++h) {
                 const int r = h * 8 + prow;
                 const u32x4_t t = __builtin_bit_cast(
-                    u32x4_t, *(const bf16x8_t*)(stg + r * 128 + ((pslot ^ ((r >> 1) & 7)) << 4)));
+                    u32x4_t, *(const bf16x8_t*)(stg + r * 128 + ((pslot ^ key_plain(r)) << 4)));
                 const int n = n0 + wn * (16 * TN) + 16 * i + r;
                 if (n >= p.N || m2 >= p.M) continue;
                 u32x4_t* op = (u32x4_t*)(p.C + (((size_t)b2 * p.heads + (n >> 6)) * 64 + (n & 63)) * p.npad + t2);
-                if constexpr ((VAR & 64) != 0) __builtin_nontemporal_store(t, op);
+                if constexpr (stream_io(VAR)) __builtin_nontemporal_store(t, op);
                 else *op = t;
             }
         }
@@ -484,7 +484,7 @@ __device__ __forceinline__ void epilogue_pipe(const FpGemmArgs& p, const Acc& ac
     static_assert(TN % 4 == 0 && TM == TC && TN == TR, "wave tile");
     const int lane = lg * 16 + li;
     const int prow = lane >> 3, pslot = lane & 7;
-    const int wkey = (li >> 1) & 7;
+    const int wkey = key_plain(li);                        // slab_addr(li, slot) = wr + ((slot ^ wkey) << 4)
     const int mbase = m0 + wm * (16 * TM), nw0 = n0 + wn * (16 * TN);
     const int rows_left = max(p.M - mbase, 0);
     auto records = [&](int ld) { const unsigned long long b = (unsigned long long)rows_left * (unsigned)ld * 2ull; return (int)(b > 0x7fffffffull ? 0x7fffffffull : b); };
@@ -569,7 +569,7 @@ __device__ __forceinline__ void epilogue_pipe(const FpGemmArgs& p, const Acc& ac
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int r = h * 8 + prow;
-            t[h] = __builtin_bit_cast(u32x4_t, *(const bf16x8_t*)(stg2 + (b & 1) * EPI_STAGE_BYTES + r * 128 + ((pslot ^ ((r >> 1) & 7)) << 4)));
+            t[h] = __builtin_bit_cast(u32x4_t, *(const bf16x8_t*)(stg2 + (b & 1) * EPI_STAGE_BYTES + r * 128 + ((pslot ^ key_plain(r)) << 4)));
         }
         if constexpr (EGELU) {
             // the slab reads must have landed BEFORE the next gathers are sent: hipcc counts only its own LDS operations, so a wait it

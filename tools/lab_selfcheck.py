@@ -39,7 +39,7 @@ def main():
     bias, gamma = torch.randn((N,), generator=g).to(torch.bfloat16), torch.randn((N,), generator=g).to(torch.bfloat16)
     resid = torch.randn((M, N), generator=g).to(torch.bfloat16)
     ref0, ref2 = ops.gemm(x, w, bias, 0).cpu(), ops.gemm(x, w, bias, 2, gamma=gamma, resid=resid).cpu()
-    for var in (0, 6, 14, 46, 110, 238 | 256, 238 | 2048, 238 | 512, 238 | 8192, 238 | 16384, 238 | 65536):
+    for var in (0, 6, 14, 46, 78, 110, 238 | 256, 238 | 2048, 238 | 512, 238 | 1024, 238 | 8192, 238 | 16384, 238 | 65536):
         ops.set_option("gemm_variant", var)
         assert torch.equal(ops.gemm(x, w, bias, 0).cpu(), ref0), var
         assert torch.equal(ops.gemm(x, w, bias, 2, gamma=gamma, resid=resid).cpu(), ref2), var
@@ -92,7 +92,8 @@ def main():
                 r += [ops.ln_linear(xs, gl, bl, ws, bs, mode=0).cpu(), ops.ln_linear(xs, gl, bl, ws, bs, mode=1).cpu()]
             return r
         ref = run()
-        for var in (238 | 262144, 238 | 524288, 238 | 524288 | 262144, 238 | 1048576, 238 | 1048576 | 4096):
+        # (0 / 6: the plain and the pipelined loop on the small tiers; 131072: the 64x64 tier on two K-tile buffers)
+        for var in (0, 6, 238 | 131072, 238 | 262144, 238 | 524288, 238 | 524288 | 262144, 238 | 1048576, 238 | 1048576 | 4096):
             ops.set_option("gemm_variant", var)
             for a_, b_ in zip(ref, run()):
                 assert torch.equal(a_, b_), f"gemm_variant {var} differs from the product at {(Ms, Ns, Ks)}"
