@@ -110,7 +110,7 @@ int fp_topk_merge(fp_ctx* ctx, const float* d_cand_scores, const int32_t* d_cand
  * top-k per-view scores bf16(normalize_bf16(view) . f).  k <= 128, <= 1024 views per mesh. */
 int fp_rerank_views(fp_ctx* ctx, const void* d_views, const int32_t* d_offsets, const int32_t* d_cand,
                     const void* d_queries, int Q, int C, int D, int k, float* d_out, void* stream);
-/* F.normalize(x, dim=-1) on bf16 rows with the reference's rounding points. */
+/* F.normalize(x, dim=-1) on bf16 rows with the reference's rounding points: d_x_bf16 and d_y_bf16 bf16 [rows,D] (in place is allowed). */
 int fp_l2_normalize(fp_ctx* ctx, const void* d_x_bf16, int rows, int D, void* d_y_bf16, void* stream);
 
 /* ---- a7/a10: patchwise template score (pose_estimator.py:85-88, online_pose_estimator.py:68-79) ------- */
@@ -153,8 +153,8 @@ int fp_roi_align(fp_ctx* ctx, const float* d_images, int n_img, int C, int H, in
 /* super-Fibonacci rotations, fp64 [n,3,3] row-major written to HOST memory (one-off setup, n=600/20000). */
 int fp_generate_rotations(int n, double* h_out);
 /* indices i with geodesic(R_i, R_prev) < thresh_deg; d_grid f64 [G,3,3] (device), h_Rprev9 f64 row-major
- * (host); out idx ascending (np.where order), count in *h_n.  Synchronises the stream (the count decides
- * how many hypotheses are rendered next). */
+ * (host); count in *h_n; d_out_idx i32 [G]: the first *h_n entries are written, in ascending order (np.where order); the entries behind
+ * them are unspecified.  Synchronises the stream (the count decides how many hypotheses are rendered next). */
 int fp_geodesic_select(fp_ctx* ctx, const double* d_grid, int G, const double* h_Rprev9, double thresh_deg,
                        int32_t* d_out_idx, int* h_n, void* stream);
 
@@ -211,7 +211,7 @@ int fp_depth_extents(fp_ctx* ctx, const float* d_depth, int Hn, int Hh, int W, f
 /* ---- g: pose-error evaluation (bop_toolkit/scripts/eval_calc_errors.py:311-570 and bop_toolkit_lib/pose_error.py; the reference
  * renders with OpenGL and builds two kd-trees per estimate x ground-truth pair) ------------------------------------------------- */
 /* chamfer (pose_error.py:188-201) and, with projected = 1, chamfer_proj (:204-218) of B pairs in one call:
- *   d_out[b] = mean_y(min_x |x - y|) + mean_x(min_y |x - y|)    (chamfer_distance(direction='bi', metric='l2'), :143-185; not squared)
+ *   d_out f64 [B]: d_out[b] = mean_y(min_x |x - y|) + mean_x(min_y |x - y|)    (chamfer_distance(direction='bi', metric='l2'), :143-185; not squared)
  * over x = posed (projected) vertices of the mesh used at inference, y = those of the ground-truth model.
  * d_pts f64 [n_pts,3]: the vertex clouds of every model back to back.  d_table i32 [B,8] per pair: {first row of the estimate's cloud in
  * d_pts, its size, first row of the GT cloud, its size, first slot of the two centred clouds in the workspace (each pair owns size_e +
@@ -273,7 +273,8 @@ int fp_comm_rank(const fp_ctx* ctx);
 /* all-gather `bytes` device bytes from every rank into d_recv [nranks * bytes] (rank order); a copy without a communicator */
 int fp_allgather_bytes(fp_ctx* ctx, const void* d_send, size_t bytes, void* d_recv, void* stream);
 /* bank-row sharding: every rank passes its local top-k [Q,k] with GLOBAL row indices; the candidates of all ranks
- * are gathered and merged with the canonical (score desc, index asc) rule -> identical [Q,k_out] on every rank */
+ * are gathered and merged with the canonical (score desc, index asc) rule -> identical [Q,k_out] on every rank (d_out_scores f32,
+ * d_out_idx i32) */
 int fp_allgather_topk(fp_ctx* ctx, const float* d_scores, const int32_t* d_idx, int Q, int k, int k_out, float* d_out_scores,
                       int32_t* d_out_idx, void* stream);
 /* proposal / frame / object sharding: gather n_rows fixed-length f64 result rows per rank (every rank passes the same n_rows;
@@ -300,7 +301,7 @@ int fp_op_ln_linear(fp_ctx* ctx, const void* d_X, int M, int K, const void* d_g_
 /* fp_op_gemm with epilogue 2 (LayerScale + residual) that also emits the row statistics of what it wrote — the producer side of the
  * folded LayerNorm (per-64-column partial sums in the epilogue, summed in block order).  d_stat u32/f32 [M,6]: words 0-3 the 16-byte
  * init-MFMA record of the row as the consuming GEMM reads it — bf16 {sh, sl, sh, -mh, -ml, -mh, 0, 0}, sigma = sqrt(var + eps) and
- * -mean as two-piece bf16 splits —, word 4 rstd = 1 / sigma (f32), word 5 unused. */
+ * -mean as two-piece bf16 splits —, word 4 rstd = 1 / sigma (f32), word 5 unused (never written). */
 int fp_op_gemm_stats(fp_ctx* ctx, const void* d_X, int ldx, const void* d_W, int ldw, void* d_C, int ldc, const void* d_bias,
                      const void* d_gamma, const void* d_resid, int ldr, int M, int N, int K, float eps, float* d_stat, void* stream);
 /* The patch-embed GEMM of fp_vit_forward (the Conv2d patch_embed.proj of hub DINOv2 behind src/pipeline/retrieval/dino.py:18 as a GEMM
@@ -350,7 +351,7 @@ int fp_op_gemm_plan(fp_ctx* ctx, int M, int N, int K, int epi, int ldx, int ldw,
  * (one line; tiles, chunks, rounds, bin and lds are 0 on the global path): the plan of csrc/raster_plan.h and the thresholds the kernels
  * were compiled with.  Host-only entry used by the tests of the rasteriser's branches. */
 int fp_op_raster_plan(fp_ctx* ctx, int W, int H, int F, int Hn, char* out, size_t out_bytes);
-/* d_y[i] = bf16(0.5 x (1 + erf(x / sqrt 2))) elementwise on bf16 values in fp32: the direct expression the fc1 epilogue's GELU table
+/* d_x and d_y bf16 [n]: d_y[i] = bf16(0.5 x (1 + erf(x / sqrt 2))) elementwise on bf16 values in fp32: the direct expression the fc1 epilogue's GELU table
  * is filled from (hub DINOv2 Mlp act_layer = nn.GELU behind src/pipeline/retrieval/dino.py:18-19); the table-GELU GEMM is tested
  * against it on all 65 536 bf16 inputs */
 int fp_op_gelu(const void* d_x, void* d_y, size_t n, void* stream);
@@ -359,6 +360,7 @@ int fp_op_gelu(const void* d_x, void* d_y, size_t n, void* stream);
  * LayerNorm-folded qkv weights — fp_op_ln_linear's n_scaled / row_scale — so the softmax needs no multiply-add per element) */
 int fp_op_attention(const void* d_QK, int ldqk, const void* d_Vt, void* d_O, int ldo, int B, int H, int n_tok,
                     int npad, int q_prescaled, void* stream);
+/* nn.LayerNorm over the last dimension with bf16 rounding of the result: d_X and d_Y bf16 [rows,D], d_gamma and d_beta bf16 [D] */
 int fp_op_layernorm(const void* d_X, void* d_Y, const void* d_gamma, const void* d_beta, int rows, int D, float eps,
                     void* stream);
 /* ImageNet normalise (torchvision Normalize on a bf16 tensor: subtract, round, divide, round — src/pipeline/retrieval/dino.py:12,16) +
@@ -367,7 +369,7 @@ int fp_op_layernorm(const void* d_X, void* d_Y, const void* d_gamma, const void*
 int fp_op_im2col_norm(const void* d_img, void* d_A, int B, int H, int W, int ps, int KP, void* stream);
 /* The other helper kernels of the towers, one at a time (kernel-level entries used by the tests).  All tensors bf16 unless said
  * otherwise; a call with no rows / no elements returns 0 without launching anything.
- * fp_op_layernorm with the launch form of the towers' final norm: output row r reads input row
+ * fp_op_layernorm with the launch form of the towers' final norm, d_Y [rows,D]: output row r reads input row
  * (r / rows_per_b) * in_stride_b + in_off + r % rows_per_b (rows_per_b <= 0: row r); l2_normalize != 0 writes every row
  * F.normalize()d with fp_l2_normalize's arithmetic (D <= 1536).  D: a multiple of 8 up to 2048. */
 int fp_op_layernorm_rows(const void* d_X, void* d_Y, const void* d_gamma, const void* d_beta, int rows, int D, float eps, int rows_per_b,
@@ -495,7 +497,7 @@ int fp_pnp_epnp(fp_ctx* ctx, const double* d_pts3d, const double* d_pts2d, const
 /* A classical stand-in for the learned tracker the reference fetches from torch.hub (CoTracker2): Bouguet's pyramidal Lucas-Kanade, a
  * different kind of tracker with no parity claim against the reference, and not pinned to OpenCV's calcOpticalFlowPyrLK either.  The
  * algorithm is stated in DESIGN.md section 18 and csrc/lk_core.h and pinned to the numpy restatement tests/_lk_ref.py.
- * fp_lk_pyramid: d_frames u8 [T,H,W,3] (RGB) -> d_pyramid f32, the levels back to back, level l = [T, h_l, w_l] with h_0 = H, w_0 = W,
+ * fp_lk_pyramid: d_frames u8 [T,H,W,3] (RGB) -> d_pyramid f32 [n_floats], the levels back to back, level l = [T, h_l, w_l] with h_0 = H, w_0 = W,
  * h_l = (h_{l-1} + 1) / 2.  Level 0 is Y = (77 R + 150 G + 29 B + 128) >> 8; level l is level l-1 under the separable [1 4 6 4 1] / 16,
  * rows then columns, replicate border, even pixels kept: (((a + e) + 4 (b + d)) + 6 c) / 16 in fp32 without FMA, bit for bit a float32
  * numpy restatement.  `levels` (1..8) is a request: a level whose smaller side is below 2 radius + 1 is dropped with all coarser ones,
@@ -548,8 +550,8 @@ int fp_lk_track(fp_ctx* ctx, const float* d_pyramid, int T, int H, int W, int le
  * o = R_e^T (x - t_e), kept when |o| < est_scale; the mean of the kept o, its length limited to est_scale / 2; t_e <- R_e o + t_e (no
  * frame kept: unchanged).
  * -> d_per_offset f64 [M,D,3]: mean over the N - dt pairs / dt, for (rot, proj, depth); d_final f64 [M,3]: the mean over the D offsets,
- * rot in degrees, proj / sqrt(w^2 + h^2) * 100.  Optional (NULL = not wanted): d_aligned f64 [M,Nmax,3] the moved translations,
- * d_pairs f64 [M,D,Nmax,3] the per-pair errors (rows t1 >= N - dt are left as they are).
+ * rot in degrees, proj / sqrt(w^2 + h^2) * 100.  Optional (NULL = not wanted): d_aligned f64 [M,Nmax,3] the moved translations (rows past
+ * a track's own length are left as they are), d_pairs f64 [M,D,Nmax,3] the per-pair errors (rows t1 >= N - dt are left as they are).
  * No floating-point atomics, every sum in a fixed order: two calls give the same bits. */
 int fp_video_errors(fp_ctx* ctx, const double* d_est, const double* d_gt, const int32_t* h_meta, const double* h_params, int M, int V,
                     int Nmax, int D, double* d_per_offset, double* d_final, double* d_aligned, double* d_pairs, void* stream);
